@@ -1,7 +1,7 @@
 """bench.py -- frames/s of the MsSVT backbone on MI355X (BASELINE.json metric).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--points 160000] [--batch 1]
-                    [--attn-dtype f32|bf16] [--train] [--cfg yaml]
+                    [--attn-dtype f32|bf16] [--train] [--cfg yaml] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one backbone forward (voxel_coords, voxel_features -> encoded SparseTensor, eval mode)
@@ -16,12 +16,25 @@ bf16`` is configs[2]; ``--gpus 8 --batch 4`` the per-GPU shape of configs[3].
 output and exits with their status.  Scenes are sharded by rank (no data-path collective; weak
 scaling); the time is the max over ranks between barriers.
 
-Prints ONE JSON line on rank 0 with the driver's contract fields plus
+Prints ONE JSON line on rank 0 with the driver's contract fields (metric, value, unit, higher_is_better, dtype,
+ms_per_step = the milliseconds of one of the K timed steps) and the configuration that ran.  A plain run does only that:
+set up, warm up, time the K steps, write the outputs (--dump-outputs), print the line.  ``--full`` adds, after the timed
+steps and outside them,
   "timing":       median / p10 / p90 of >= 50 steps timed one by one with HIP events (SURVEY 8d);
+  "one_frame_in_flight": with frames in flight, the same K steps one at a time on one stream;
   "roofline":     the dominant kernel (k_ffn_ws: the FFN tail in one launch, HBM bound) measured live with HIP events, and
-                  "frame": the whole frame's algorithmic bytes / FLOP against both roofs;
+                  "frame": the whole frame's algorithmic bytes / FLOP against both roofs (off with --no-roofline);
   "cpu_baseline": the CPU oracle (a port of the reference's CUDA semantics; the reference has no CPU
-                  path) timed on this box's host: the whole forward on all cores and on one thread.
+                  path) timed on the host: the whole forward on all cores and on one thread (off with --no-cpu-baseline);
+  config.output_voxels: the output rows of frame 0, run once more (also with --from-points, whose byte count reads it;
+                  a --train line always reports its last step's).
+
+``--dump-outputs DIR``: right after the timed steps, rank 0 writes what the last timed step returned to its caller --
+every array of the output dict that is not an input of the step (the SparseTensor as ``<key>.features`` /
+``<key>.indices``) -- as ``DIR/<name>.npy``, floating point as float32 (float64 stays float64), integers as float64.
+Above 64 MiB in all, every array is replaced by a fixed seeded sample of its flattened elements, written beside the
+flat positions it took (``DIR/<name>.index.npy``).  The inputs depend on the arguments alone (seeded generators), so two
+builds can be compared output for output.
 """
 import argparse
 import json
@@ -76,6 +89,11 @@ def parse(argv=None):
                          "default: pipeline.auto_depth(batch) -- 4 below four scenes per step, 1 from there on")
     ap.add_argument("--frames", type=int, default=4,
                     help="distinct resident frames the steps rotate over (1: the same frame from the same addresses every step)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure per-step timing, one frame in flight, the roofline and the CPU "
+                         "baseline (module docstring); off: the headline figure only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (module docstring)")
     args = ap.parse_args(argv)
     if args.in_flight is None:
         from mssvt_amd.pipeline import auto_depth
@@ -137,6 +155,50 @@ def per_step_times_ms(step, iters):
         e1.record()
     torch.cuda.synchronize()
     return sorted(e0.elapsed_time(e1) for e0, e1 in evs)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def output_arrays(out, inputs):
+    """{name: numpy array} of a step's output dict without its `inputs` keys: tensors as they are, a SparseTensor as
+    `<key>.features` / `<key>.indices`; floating point as float32 (float64 kept), integers and booleans as float64."""
+    import numpy as np
+    from mssvt_amd.pipeline import FramePipeline
+    out = FramePipeline.result(out)
+    arrays = {}
+
+    def put(name, t):
+        a = t.detach().cpu().numpy()
+        arrays[name] = a.astype(a.dtype if a.dtype == np.float64 else
+                                np.float32 if np.issubdtype(a.dtype, np.floating) else np.float64)
+    for key in sorted(out):
+        v = out[key]
+        if key in inputs:
+            continue
+        if isinstance(v, torch.Tensor):
+            put(key, v)
+        elif hasattr(v, "features") and hasattr(v, "indices"):
+            put(key + ".features", v.features)
+            put(key + ".indices", v.indices)
+    return arrays
+
+
+def dump_outputs(arrays, dirname, limit=DUMP_LIMIT_BYTES):
+    """Write `arrays` as DIR/<name>.npy; above `limit` bytes in all, a seeded sample of every array's flattened elements
+    (the same positions for arrays of the same size) and those positions as DIR/<name>.index.npy (float64)."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    # a sampled element costs its own bytes + 8 for its position
+    frac = 1.0 if total <= limit else limit / float(sum(a.size * (a.itemsize + 8) for a in arrays.values()))
+    for name, a in arrays.items():
+        if frac < 1.0:
+            keep = int(a.size * frac)
+            pos = np.sort(np.random.default_rng(0).choice(a.size, keep, replace=False))
+            np.save(os.path.join(dirname, name + ".index.npy"), pos.astype(np.float64))
+            a = a.reshape(-1)[pos]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def cpu_model():
@@ -427,36 +489,44 @@ def main():
     if pipe is not None:
         pipe.synchronize()
     elapsed, out = mdist.timed_steps(step, args.steps, dist, dev, sync=full_sync)
-    # SURVEY 8(d) protocol beside the driver's K-step clock: every step between two HIP events
-    # (a training step is collective -- every rank takes part; the forward is not, rank 0 measures alone)
-    # (one frame at a time on one stream: a step's duration = its latency; the pipelined steps overlap)
+    if args.dump_outputs and rank == 0:  # before anything else runs on the frames' workspaces
+        points_in = (args.from_points and not args.train) or (args.train and args.detector)
+        inputs = {"points", "batch_size", "gt_boxes"} if points_in else {"voxel_features", "voxel_coords", "batch_size"}
+        dump_outputs(output_arrays(out, inputs), args.dump_outputs)
     one = step_alone or step
-    times = per_step_times_ms(one, max(50, args.steps)) if (rank == 0 or args.train) else None
-    alone = None
-    if step_alone is not None and step is not step_alone and rank == 0:
-        for _ in range(3):
-            step_alone()
-        alone, _ = mdist.timed_steps(step_alone, args.steps, None, dev)
-    # live roofline: the same K steps once more on rank 0 with HIP events around every launch of the
-    # dominant kernel (kept out of the timed region above: the event markers cost ~3 % of the frame rate)
-    live = None
+    times = alone = live = None
     std = rank == 0 and impl == "fused" and not args.cfg and not args.train and not args.from_points
-    if std and not args.no_roofline:
-        from mssvt_amd import fused
-        fused.FFN_TIMER = []
-        for _ in range(args.steps):
-            one()
-        torch.cuda.synchronize()
-        live = fused.ffn_timer_summary(fused.FFN_TIMER)
-        fused.FFN_TIMER = None
+    if args.full:
+        # SURVEY 8(d) protocol beside the driver's K-step clock: every step between two HIP events
+        # (a training step is collective -- every rank takes part; the forward is not, rank 0 measures alone)
+        # (one frame at a time on one stream: a step's duration = its latency; the pipelined steps overlap)
+        times = per_step_times_ms(one, max(50, args.steps)) if (rank == 0 or args.train) else None
+        if step_alone is not None and step is not step_alone and rank == 0:
+            for _ in range(3):
+                step_alone()
+            alone, _ = mdist.timed_steps(step_alone, args.steps, None, dev)
+        # live roofline: the same K steps once more on rank 0 with HIP events around every launch of the
+        # dominant kernel (kept out of the timed region above: the event markers cost ~3 % of the frame rate)
+        if std and not args.no_roofline:
+            from mssvt_amd import fused
+            fused.FFN_TIMER = []
+            for _ in range(args.steps):
+                one()
+            torch.cuda.synchronize()
+            live = fused.ffn_timer_summary(fused.FFN_TIMER)
+            fused.FFN_TIMER = None
 
     if rank == 0:
-        if not args.train:  # frame 0 once more (outside every timed region): the output cpu_baseline checks against the oracle
-            one = step_alone or step
+        sp_out = None
+        if args.train:
+            sp_out = out["encoded_spconv_tensor"]
+        elif args.full or points_line is not None:
+            # frame 0 once more (outside every timed region): the output cpu_baseline checks against the oracle and the
+            # --from-points byte count reads
             turn[0] = 0
             out = one()
             torch.cuda.synchronize()
-        sp_out = out["encoded_spconv_tensor"]
+            sp_out = out["encoded_spconv_tensor"]
         ms = 1e3 * elapsed / args.steps
         arith = arith_of(net) if not args.train else (
             "compact training path (mssvt_amd/train_path.py): pair attention on fp32 vector FMAs, linears on split-fp16 operands",
@@ -490,11 +560,12 @@ def main():
                        "parallelism": "scenes sharded over %d GPU(s), %s" % (
                            world, "DDP gradient all-reduce (%s)" % backend if args.train else "no data-path collective"),
                        "process_group": {"backend": backend if dist else None, "world_size": seen_world}},
-            "timing": {"protocol": "each of %d further steps between two HIP events on the launching stream" % len(times),
-                       "median_ms": times[len(times) // 2], "p10_ms": times[len(times) // 10],
-                       "p90_ms": times[(len(times) * 9) // 10], "frames_per_s_at_median":
-                           args.batch / (times[len(times) // 2] * 1e-3)},
         }
+        if times is not None:
+            res["timing"] = {"protocol": "each of %d further steps between two HIP events on the launching stream" % len(times),
+                             "median_ms": times[len(times) // 2], "p10_ms": times[len(times) // 10],
+                             "p90_ms": times[(len(times) * 9) // 10], "frames_per_s_at_median":
+                                 args.batch / (times[len(times) // 2] * 1e-3)}
         if points_line is not None:
             bev = out["spatial_features"]
             dense_bytes = 4.0 * bev.numel() + 4.0 * sp_out.features.numel()
@@ -515,10 +586,10 @@ def main():
                 "note": "the same %d steps one at a time on one stream (what rounds 1-4 reported as value); the headline keeps %d "
                         "independent frames in flight, each on its own HIP stream and workspace (mssvt_amd/pipeline.py; every "
                         "frame bit-identical to the frame run alone: tests/test_pipeline_gpu.py)" % (args.steps, args.in_flight)}
-        if std and not args.no_roofline:
+        if std and args.full and not args.no_roofline:
             res["roofline"] = roofline.measure(net, vc, feats, args.batch, event_time_ms, HBM_PEAK_GBS, live=live,
                                                ms_per_step=ms)
-        if std and not args.no_cpu_baseline and world == 1:
+        if std and args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(net, cfg, vc_np, feats_np, args.batch, gpu_out=sp_out)
         print(json.dumps(res), flush=True)
     if pipe is not None:

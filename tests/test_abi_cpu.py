@@ -4,8 +4,6 @@ import ctypes
 import os
 import re
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -79,32 +77,27 @@ def test_product_has_no_oracle_import_and_fails_loudly_without_library(monkeypat
         raise AssertionError("missing library must raise")
 
 
-def test_pybind_stand_ins_cover_every_call_of_the_reference_python():
+def test_pybind_stand_ins_cover_every_call_of_the_reference_python(golden_dir):
     """Every `mssvt_ops_cuda.<f>(...)` / `pointnet2.<f>(...)` call in the reference's own op files that the path uses
-    must exist in the stand-in modules with the same number of positional parameters (build container only: the
-    reference tree is not shipped)."""
-    import ast
-    import inspect
-    ref = "/root/reference/pcdet/ops"
-    files = {"mssvt_ops_cuda": (os.path.join(ref, "mssvt", "mssvt_ops.py"), "mssvt_amd.mssvt_ops_compat"),
-             "pointnet2": (os.path.join(ref, "pointnet2", "pointnet2_batch", "pointnet2_utils.py"),
-                           "mssvt_amd.pointnet2_compat")}
-    if not all(os.path.exists(f) for f, _ in files.values()):
-        pytest.skip("reference tree not present")
+    must exist in the stand-in modules with the same number of positional parameters (the calls and their argument
+    counts as recorded from the reference tree: tests/golden/reference_op_calls.json)."""
     import importlib
+    import inspect
+    import json
+    with open(os.path.join(golden_dir, "reference_op_calls.json")) as f:
+        calls = json.load(f)["calls"]
+    modules = {"mssvt_ops_cuda": "mssvt_amd.mssvt_ops_compat", "pointnet2": "mssvt_amd.pointnet2_compat"}
+    assert {c["module"] for c in calls} == set(modules)
     off_path = {"ball_query_wrapper", "three_interpolate_wrapper", "three_interpolate_grad_wrapper"}  # SURVEY 8a
     seen = 0
-    for alias, (path, modname) in files.items():
+    for c in calls:
+        modname, name = modules[c["module"]], c["function"]
         mod = importlib.import_module(modname)
-        for node in ast.walk(ast.parse(open(path).read())):
-            if (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute)
-                    and isinstance(node.func.value, ast.Name) and node.func.value.id == alias):
-                name = node.func.attr
-                assert hasattr(mod, name), "%s.%s missing" % (modname, name)
-                if name in off_path:
-                    continue
-                params = inspect.signature(getattr(mod, name)).parameters
-                assert len(params) == len(node.args), "%s: %d parameters, the reference passes %d" % (
-                    name, len(params), len(node.args))
-                seen += 1
+        assert hasattr(mod, name), "%s.%s missing" % (modname, name)
+        if name in off_path:
+            continue
+        params = inspect.signature(getattr(mod, name)).parameters
+        assert len(params) == c["positional_args"], "%s: %d parameters, the reference passes %d" % (
+            name, len(params), c["positional_args"])
+        seen += 1
     assert seen >= 10

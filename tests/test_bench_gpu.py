@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -40,13 +41,13 @@ def test_bench_ddp_training_step_two_ranks():
 
 
 def test_bench_configs2_flags():
-    res = _bench("--batch", "2", "--attn-dtype", "bf16")
+    res = _bench("--batch", "2", "--attn-dtype", "bf16", "--full")
     assert res["dtype"] == "bf16" and res["config"]["attn_dtype"] == "bf16" and res["n_gpus"] == 1
     assert res["timing"]["p10_ms"] <= res["timing"]["median_ms"] <= res["timing"]["p90_ms"]
 
 
 def test_bench_ffn_arith_flag_and_roofline_object():
-    """--ffn-arith selects the FFN / CompressBlock arithmetic and the JSON says which one ran; the default line carries the
+    """--ffn-arith selects the FFN / CompressBlock arithmetic and the JSON says which one ran; the --full line carries the
     roofline of the dominant kernel (k_ffn_ws, HBM bound) with the whole-frame object."""
     res = _bench("--ffn-arith", "f32")
     assert "v_mfma_f32_16x16x4_f32" in res["config"]["ffn_arith"]
@@ -54,7 +55,7 @@ def test_bench_ffn_arith_flag_and_roofline_object():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--points", "20000",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=420, env=e, cwd=ROOT)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=420, env=e, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-800:], r.stderr[-1500:])
     res = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
     assert res["config"]["ffn_arith"].startswith("split16") and "two fp16 halves" in res["config"]["ffn_arith"]
@@ -86,10 +87,28 @@ def test_bench_arith_f32_in_flight_and_from_points():
     assert res["config"]["arith"] == "f32" and "v_mfma_f32_16x16x4_f32" in res["config"]["ffn_arith"]
     assert res["config"]["attn_arith"] == "f32: v_mfma_f32_16x16x4_f32" and res["config"]["frames_in_flight"] == 1
     assert all(b["ffn"] == "f32" and b["attn"] == "f32" for b in res["config"]["arith_per_block"])
-    res = _bench("--in-flight", "3")
+    res = _bench("--in-flight", "3", "--full")
     assert res["config"]["frames_in_flight"] == 3 and res["one_frame_in_flight"]["value"] > 0
     assert "mssvt_frame_forward" in res["config"]["host_path"]
     res = _bench("--from-points")
     fp = res["from_points"]
     assert fp["points"] == 20000 and fp["voxels"] > 5000 and fp["bev_shape"][1] == 128 and 0 < fp["frac"] < 1
     assert fp["algorithmic_bytes"] == fp["vfe_bytes"] + fp["backbone_bytes"] + fp["dense_bytes"]
+
+
+def test_bench_plain_line_and_dump_outputs(tmp_path):
+    """A plain run prints the headline only (no measurement beyond its K timed steps: that is --full); --dump-outputs writes
+    what the last timed step returned, and two runs with the same arguments write the same arrays."""
+    dirs = [str(tmp_path / "a"), str(tmp_path / "b")]
+    lines = [_bench("--dump-outputs", d) for d in dirs]
+    for res in lines:
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(res)
+        assert not {"timing", "one_frame_in_flight", "roofline", "cpu_baseline"} & set(res)
+        assert res["steps"] == 3 and abs(res["value"] - 3 / (res["ms_per_step"] * 3e-3)) < 1e-6 * res["value"]
+    names = ["encoded_spconv_tensor.features.npy", "encoded_spconv_tensor.indices.npy"]
+    assert sorted(os.listdir(dirs[0])) == sorted(os.listdir(dirs[1])) == names
+    feats, idx = [np.load(os.path.join(dirs[0], n)) for n in names]
+    assert feats.dtype == np.float32 and feats.shape[1] == 128 and np.isfinite(feats).all()
+    assert idx.dtype == np.float64 and idx.shape == (feats.shape[0], 4) and (idx[:, 0] == 0).all()
+    for n in names:
+        np.testing.assert_array_equal(np.load(os.path.join(dirs[0], n)), np.load(os.path.join(dirs[1], n)))

@@ -1,7 +1,7 @@
 #!/bin/bash
 out=gpurun_out/r06d; mkdir -p $out
 line() { python -c "import json,sys;d=json.loads([l for l in open('$1') if l.startswith('{')][-1]);print('$1',round(d['value'],1),d['unit'],round(d['ms_per_step'],3),'ms', (d.get('one_frame_in_flight') or {}).get('value'))"; }
-b() { name=$1; shift; timeout 400 python bench.py --no-cpu-baseline --no-roofline "$@" > $out/$name.json 2>> $out/bench.err; line $out/$name.json; }
+b() { name=$1; shift; timeout 400 python bench.py --full --no-cpu-baseline --no-roofline "$@" > $out/$name.json 2>> $out/bench.err; line $out/$name.json; }
 for k in priority cumask; do
   MSSVT_PIPE_STREAMS=$k b s20_$k --steps 20 --warmup 5
   MSSVT_PIPE_STREAMS=$k b s50_$k --steps 50

@@ -1,7 +1,7 @@
 #!/bin/bash
 out=gpurun_out/r06e; mkdir -p $out
 line() { python -c "import json,sys;d=json.loads([l for l in open('$1') if l.startswith('{')][-1]);print('$1',round(d['value'],1),d['unit'],round(d['ms_per_step'],3),'ms', (d.get('one_frame_in_flight') or {}).get('value'))"; }
-b() { name=$1; shift; timeout 400 python bench.py --no-cpu-baseline --no-roofline "$@" > $out/$name.json 2>> $out/bench.err; line $out/$name.json; }
+b() { name=$1; shift; timeout 400 python bench.py --full --no-cpu-baseline --no-roofline "$@" > $out/$name.json 2>> $out/bench.err; line $out/$name.json; }
 timeout 900 python -m pytest tests/test_vfe_gpu.py -x -q > $out/pytest_vfe.txt 2>&1; echo "pytest vfe rc $?"; tail -3 $out/pytest_vfe.txt
 ROWS=45 bash tools/prof.sh r06e_pts_one --steps 20 --in-flight 1 --from-points > $out/prof_pts_one.txt; grep "k_ps_\|k_vox\|k_dense" $out/prof_pts_one.txt | cut -c1-120
 b from_points --from-points
@@ -11,7 +11,7 @@ for k in priority cumask priority cumask; do
 done
 b one --in-flight 1
 MSSVT_XCD_REMAP=0 b one_r0 --in-flight 1
-timeout 600 python bench.py --no-cpu-baseline > $out/bench_roofline.json 2>> $out/bench.err; line $out/bench_roofline.json
+timeout 600 python bench.py --full --no-cpu-baseline > $out/bench_roofline.json 2>> $out/bench.err; line $out/bench_roofline.json
 python - <<'PY'
 import json
 d=json.loads([l for l in open('gpurun_out/r06e/bench_roofline.json') if l.startswith('{')][-1])
