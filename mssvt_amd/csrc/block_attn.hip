@@ -40,7 +40,6 @@
 //
 // Windows (B) are processed in the plan's work order (heaviest first), dealt round-robin to the
 // wavefronts of a persistent grid.
-#include <stdlib.h>
 #include "common.hip.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -74,7 +73,6 @@ struct AttnArgs {
     float *attn;
     int row_capacity;  // rows of qbuf / the compact row arrays
     const void *packed;  // split-fp16 weight fragments of this group (mssvt_attn_pack_weights) or null
-    int xcd;  // deal the work order so that an XCD owns a contiguous run per round (common.hip.h, xcd_contiguous_block)
 };
 
 // head groups of equal shape run in ONE launch: blockIdx.y = group (their work is independent: channel
@@ -647,8 +645,7 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_q16(Att
 }
 
 // ---- C, kv16 form: Xbar -> attention output rows
-// VIN (round 6): the hand-off rows hold V (k_attn_kvh<.., VOUT>): only the output projection is left
-template <int CG, int HP, bool VIN = false>
+template <int CG, int HP>
 __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_o16(AttnPack pack) {
     const AttnArgs &a = pack.g[blockIdx.y];
     using L = AttnBlob<CG>;
@@ -671,7 +668,7 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_o16(Att
             dst_[S] = f32x4{t4_.x, t4_.y, t4_.z, t4_.w};                                                  \
         }                                                                                                 \
     }
-    if (!VIN) ATTN_O16_ROWS(x, min(tile * 16 + r, rows - 1), 0)
+    ATTN_O16_ROWS(x, min(tile * 16 + r, rows - 1), 0)
     attn_stage16<(L::WK2 - L::WV) / 16, ATTN_QO16_WAVES * MSSVT_WAVE>(
         lds4, reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.packed) + L::WV));
     if (threadIdx.x < CG) {
@@ -683,18 +680,11 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_o16(Att
         const int row = min(tile * 16 + r, rows - 1);
         const bool row_ok = tile * 16 + r < rows;
         const int dest = a.qrow_src[row].y;
-        if (!first && !VIN) ATTN_O16_ROWS(x, row, 0)
+        if (!first) ATTN_O16_ROWS(x, row, 0)
         // GEMM3^T: V^T[o][row] = sum_c Wv[o][c] Xbar_{head(o)}[row][c] + bv[o]  (head of tile t = t)
         f32x4 v[NT];
-        if (VIN) {  // V of head t: 16 floats at the start of the (row, head) slot, this lane's o = 16 t + 4 g + i
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const float4 t4 = *reinterpret_cast<const float4 *>(a.qbuf + (size_t)row * QROW + t * CG + 4 * g);
-                v[t] = f32x4{t4.x, t4.y, t4.z, t4.w};
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < NT && !VIN; ++t) {
+        for (int t = 0; t < NT; ++t) {
             if (t + 1 < NT) ATTN_O16_ROWS(xn, row, t + 1)  // the next head's row pieces under this head's products
             const float4 b = *reinterpret_cast<const float4 *>(bv_l + 16 * t + 4 * g);
             f32x4 mm = f32x4{b.x, b.y, b.z, b.w}, cr = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1043,25 +1033,12 @@ __device__ __forceinline__ h16x4 lds_read_tr16(const char *p) {
     return __builtin_bit_cast(h16x4, __builtin_amdgcn_ds_read_tr16_b64_v4f16(
         (__attribute__((address_space(3))) fp16v4 *)(p)));
 }
-// KVH_QT_AHEAD = 1: the first-pass Qt fragments of a window are requested one window ahead like its key rows (16 more
-// VGPRs: 3 waves / SIMD).  Measured on one box (tools/ab_kvh.sh): 94.2 / 46.9 us per Block attention against 91.6 / 45.5
-// without -- the window launch is not waiting for these loads, it is short of vector-memory issue slots (round-3 timing-only ablation builds, DESIGN.md section 4:
-// dropping the 4 Qt loads of a pass -7.3 us, the 4 Xbar stores -5.9 us, serving the key rows from 8 hot rows -0.6 us).
-#ifndef KVH_QT_AHEAD
-#define KVH_QT_AHEAD 0
-#endif
 // QP: the hand-off rows hold Q' fragments (k_attn_q16<.., 2>) and Qt_h = (scale Wk_h)^T q'_h is formed here, per pass, from the
 // Wk fragments of the pack blob staged into the LDS: one product per head with the columns of the other heads zeroed in
 // the B operand, all accumulated into one tile -- NH x NT x 3 K = 16 instructions for 1 instead of 4 row loads per lane
-// VOUT (round 6, MSSVT_ATTN_VFUSE=1): V_h = Wv_h Xbar_h + bv_h is formed HERE, per pass, and the hand-off row holds V (16 floats per
-// query and head) instead of Xbar (Cg floats): every output tile of Wv (= one head, HD = 16) times the pass's Xbar columns, a
-// lane keeps the tile of ITS column's head -- NT x NP x 3 more instructions and one operand split per pass for a quarter of
-// the hand-off bytes; k_attn_o16<.., VIN> then only applies Wo.  The Wv fragments (16 KiB per group) join the Wk pair
-// fragments in the LDS, so the workgroup becomes NWV = 12 waves sharing one copy: 32 + 12 x 9 KiB, still 3 waves per SIMD.
-template <int CG, int HD, int HP, int KT, bool QP, bool VOUT = false, int NWV = ATTN_ROW_WAVES>
-__global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP ? 3 : 4) : 2) k_attn_kvh(AttnPack pack) {
-    static_assert(!QP || (HD == 16 && (CG / HD) % 2 == 0 && !KVH_QT_AHEAD), "Q' hand-off: head = one 16-row tile, heads in pairs");
-    static_assert(!VOUT || (QP && HP * HD == CG), "V hand-off: Q' mode, one output tile of Wv per head");
+template <int CG, int HD, int HP, int KT, bool QP>
+__global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 : 4) : 2) k_attn_kvh(AttnPack pack) {
+    static_assert(!QP || (HD == 16 && (CG / HD) % 2 == 0), "Q' hand-off: head = one 16-row tile, heads in pairs");
     static_assert(CG % 32 == 0 && KT % 2 == 0, "32-channel and 32-key steps");
     const AttnArgs &a = pack.g[blockIdx.y];
     constexpr int NT = CG / 16, NP = CG / 32, NS = KT / 2, NH = CG / HD, QROW = HP * CG, QPP = 16 / HP;
@@ -1069,14 +1046,12 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
     extern __shared__ float4 lds4[];
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = threadIdx.x / MSSVT_WAVE;
-    // bytes of fragments in front of the images: the Wk pair fragments (+ the Wv fragments of the V hand-off)
-    constexpr int WKB = QP ? (VOUT ? AttnBlob<CG>::BYTES : AttnBlob<CG>::WV2) - AttnBlob<CG>::WK2 : 0;
-    const h16x8 *WvF2 = reinterpret_cast<const h16x8 *>(reinterpret_cast<const char *>(lds4) + (AttnBlob<CG>::WV2 - AttnBlob<CG>::WK2));
-    (void)WvF2;
+    // bytes of fragments in front of the images: the Wk pair fragments
+    constexpr int WKB = QP ? AttnBlob<CG>::WV2 - AttnBlob<CG>::WK2 : 0;
     char *Ti = reinterpret_cast<char *>(lds4) + WKB + (size_t)wv * 2 * IMG;
     const h16x8 *WkF2 = reinterpret_cast<const h16x8 *>(lds4);
     if (QP) {  // before any wave can leave: every wave of the workgroup meets at the barrier
-        attn_stage16<(WKB > 0 ? WKB : 16) / 16, NWV * MSSVT_WAVE>(
+        attn_stage16<(WKB > 0 ? WKB : 16) / 16, ATTN_ROW_WAVES * MSSVT_WAVE>(
             lds4, reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.packed) + AttnBlob<CG>::WK2));
         __syncthreads();
     }
@@ -1091,23 +1066,9 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
         wctr[u] = g < 3 ? wp[3 + g] : 0.f;
     }
     const int n_act = __builtin_amdgcn_readfirstlane(*a.num_wins);
-    const int wstep = gridDim.x * NWV;
+    const int wstep = gridDim.x * ATTN_ROW_WAVES;
     const int K = a.K;
-    // XCD-aware deal of the work order (MSSVT_XCD_REMAP=2; off by default until measured faster): neighbours in the order are
-    // neighbours in space inside a weight class and share key rows, and every XCD has an L2 of its own.  Whole contiguous runs
-    // per XCD (common.hip.h, xcd_contiguous_block) cut the HBM traffic 114.1 -> 106.3 MB per launch but cost 106k -> 116k cycles:
-    // the order is heaviest-first, and a contiguous eighth of a round hands one XCD the heaviest windows of every round.  So:
-    // CHUNKS of 24 consecutive entries, dealt round-robin to the XCDs -- every XCD sees the whole weight range of a round.
-    int wi;
-    {
-        const int per_xcd = (int)(gridDim.x >> 3) * NWV;
-        if (a.xcd > 1 && (gridDim.x & 7) == 0 && per_xcd % 24 == 0) {
-            const int x = blockIdx.x & 7, idx = (int)(blockIdx.x >> 3) * NWV + wv;
-            wi = __builtin_amdgcn_readfirstlane(((idx / 24) * 8 + x) * 24 + idx % 24);
-        } else {
-            wi = __builtin_amdgcn_readfirstlane(blockIdx.x * NWV + wv);
-        }
-    }
+    int wi = __builtin_amdgcn_readfirstlane(blockIdx.x * ATTN_ROW_WAVES + wv);
     if (wi >= n_act) return;
     const __amdgpu_buffer_rsrc_t xr_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.xhat), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t km_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(a.kmeta), 0, -1, 0x00020000);
@@ -1155,26 +1116,7 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
     w_p = a.perm[min(wi + wstep, w_last)];
     const int hh = la % HP;
     const bool head_ok = hh < NH;
-    // V hand-off: this lane's four outputs of its column's head, o = 16 hh + 4 g + i
-    const float4 bv4 = VOUT ? *reinterpret_cast<const float4 *>(a.bkv + CG + 16 * (head_ok ? hh : 0) + 4 * g) : make_float4(0.f, 0.f, 0.f, 0.f);
-    // first-pass Qt fragments of a window travel one window ahead as well (stage R): issued before the previous window's
-    // Xbar stores, so that waiting for them never waits for those stores (vmcnt retires in order)
-    h16x8 qh_r[NP], ql_r[NP];
-    (void)qh_r; (void)ql_r;
-#define KVH_ISSUE_QT()                                                                     \
-    {                                                                                      \
-        const int nq_ = qbase_r + nqv_r <= a.row_capacity ? nqv_r : 0;                     \
-        const h16x8 *qr_ = reinterpret_cast<const h16x8 *>(                                \
-            a.qbuf + ((size_t)qbase_r + max(min(la / HP, nq_ - 1), 0)) * QROW + (head_ok ? hh : 0) * CG); \
-        _Pragma("unroll") for (int P = 0; P < NP; ++P) {                                   \
-            qh_r[P] = qr_[(P * 4 + g) * 2];                                                \
-            ql_r[P] = qr_[(P * 4 + g) * 2 + 1];                                            \
-        }                                                                                  \
-    }
     KVH_ISSUE_ROWS()
-#if KVH_QT_AHEAD
-    KVH_ISSUE_QT()
-#endif
     KVH_LOAD_META()
     w_p = a.perm[min(wi + 2 * wstep, w_last)];
     // transposed reads: lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of its 4 x 16 block
@@ -1218,13 +1160,6 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
             }
         }
         h16x8 qh[NP], ql[NP];
-#if KVH_QT_AHEAD
-#pragma unroll
-        for (int P = 0; P < NP; ++P) {
-            qh[P] = qh_r[P];
-            ql[P] = ql_r[P];
-        }
-#else
         h16x8 qp8 = h16x8{0, 0, 0, 0, 0, 0, 0, 0};  // Q' mode: (hi x 4 | lo x 4) of this lane's column
         if (QP) {
             qp8 = reinterpret_cast<const h16x8 *>(a.qbuf + (qbase + max(min(la / HP, nqv - 1), 0)) * QROW)[(head_ok ? hh : 0) * 4 + g];
@@ -1236,11 +1171,7 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
                 ql[P] = qr_[(P * 4 + g) * 2 + 1];
             }
         }
-#endif
         KVH_ISSUE_ROWS()
-#if KVH_QT_AHEAD
-        KVH_ISSUE_QT()
-#endif
         KVH_LOAD_META()
         w_p = a.perm[min(wi + 3 * wstep, w_last)];
         wave_lds_sync();
@@ -1334,8 +1265,6 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
             h16x8 ph[NS], pl[NS];
 #pragma unroll
             for (int s = 0; s < NS; ++s) h16_split8(sc[2 * s] * inv, sc[2 * s + 1] * inv, ph[s], pl[s]);
-            f32x4 xb[VOUT ? NT : 1];  // V hand-off: the pass's Xbar tiles stay in registers
-            (void)xb;
 #pragma unroll
             for (int u = 0; u < NT; ++u) {
                 f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
@@ -1350,47 +1279,15 @@ __global__ void __launch_bounds__(NWV *MSSVT_WAVE, KT <= 2 ? (KVH_QT_AHEAD || QP
                 }
                 const f32x4 xt = f32x4{__builtin_fmaf(cr[0], H16_INV, mm[0]), __builtin_fmaf(cr[1], H16_INV, mm[1]),
                                        __builtin_fmaf(cr[2], H16_INV, mm[2]), __builtin_fmaf(cr[3], H16_INV, mm[3])};
-                if (VOUT) {
-                    xb[VOUT ? u : 0] = xt;
-                } else if (q_ok) {  // xbar replaces qt in place (this lane's own bytes of the row)
+                if (q_ok) {  // xbar replaces qt in place (this lane's own bytes of the row)
                     // image column 16 u + 4 g + i is k slot (2 (u % 2) + g / 2, 4 (g % 2) + i) of step u / 2 (see above)
                     store_handoff(xrow + 32 * (u >> 1) + 16 * (g & 1) + 8 * (u & 1) + 4 * (g >> 1), xt);
                 }
-            }
-            if (VOUT) {
-                // V^T[o][col] = sum_c Wv[o][c] Xbar[c][col] for every head tile t; the lane keeps t = head(col).  Tiles 2 P,
-                // 2 P + 1 of Xbar are the two halves of k step P as they stand (AttnBlob::WV2 holds Wv in that order)
-                h16x8 xh[NP], xl[NP];
-#pragma unroll
-                for (int P = 0; P < NP; ++P) h16_split8(xb[VOUT ? 2 * P : 0], xb[VOUT ? 2 * P + 1 : 0], xh[P], xl[P]);
-                f32x4 vsel = f32x4{0.f, 0.f, 0.f, 0.f};
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
-#pragma unroll
-                    for (int P = 0; P < NP; ++P) {
-                        const h16x8 wh = WvF2[((t * NP + P) * 2) * 64 + lane], wl = WvF2[((t * NP + P) * 2 + 1) * 64 + lane];
-                        MFMA_H(mm, wh, xh[P]);
-                        MFMA_H(cr, wh, xl[P]);
-                        MFMA_H(cr, wl, xh[P]);
-                    }
-                    const bool mine = hh == t;
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const float vt = __builtin_fmaf(cr[i], H16_INV, mm[i]);
-                        vsel[i] = mine ? vt : vsel[i];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                const f32x4 vout = f32x4{vsel[0] + bv4.x, vsel[1] + bv4.y, vsel[2] + bv4.z, vsel[3] + bv4.w};
-                if (q_ok) store_handoff(xrow + 4 * g, vout);  // V of (query, head): the first 16 floats of its slot
             }
         }
         wave_lds_sync();  // the next window rewrites the image
     }
 #undef KVH_LOAD_META
-#undef KVH_ISSUE_QT
 #undef KVH_ISSUE_ROWS
 #undef KVH_ROW4
 }
@@ -1405,59 +1302,36 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
     // A / C: persistent over 16-row tiles, one 16-wave workgroup per CU and head group at most
     const int tiles_cap = (row_capacity + 15) / 16;
     int row_grid = tiles_cap;
-    static const int qo_wgs = getenv("MSSVT_ATTN_QO_WGS") ? atoi(getenv("MSSVT_ATTN_QO_WGS")) : 2;
-    if (row_grid > cus * qo_wgs / (2 * ng)) row_grid = cus * qo_wgs / (2 * ng);
+    if (row_grid > cus / ng) row_grid = cus / ng;
     if (row_grid < 1) row_grid = 1;
     const size_t lds_q = ((size_t)2 * CGP * LS + CGP * 8 + CGP) * 4, lds_o = ((size_t)2 * CGP * LS + 2 * CGP) * 4;
     const int K = pack.g[0].K;
     if constexpr (CG % 32 == 0) {
         if (kv16 && K > 16 && K <= 64) {  // split-fp16 operands in launch B (k_attn_kvh); A writes Qt pre-split
             constexpr int RS = KVH_RS(CG);
-            static const int kvh_wgs = getenv("MSSVT_ATTN_KVH_WGS") ? atoi(getenv("MSSVT_ATTN_KVH_WGS")) : 0;
-            const int wgs = kvh_wgs > 0 ? kvh_wgs : (K <= 32 ? (KVH_QT_AHEAD ? 3 : 4) : 2);  // resident workgroups per CU
+            const int wgs = K <= 32 ? 4 : 2;  // resident workgroups per CU
             const dim3 kv_grid(cus * wgs / ng > 0 ? cus * wgs / ng : 1, ng);
             const size_t img = (size_t)ATTN_ROW_WAVES * 2 * 16 * RS;  // per key tile of 16 slots, all waves, hi + lo
-            bool packed = HD == 16 && !KVH_QT_AHEAD;
+            bool packed = HD == 16;
             for (int g = 0; g < ng; ++g) packed = packed && pack.g[g].packed != nullptr;
             int grid16 = tiles_cap;  // 8-wave workgroups, two per CU
             if (grid16 > cus * 2 / ng) grid16 = cus * 2 / ng;
             if (grid16 < 1) grid16 = 1;
-            static const int qo16 = getenv("MSSVT_ATTN_QO16_MASK") ? atoi(getenv("MSSVT_ATTN_QO16_MASK")) : 7;  // 1: A, 2: C, 4: Q' hand-off
-            const bool q16 = packed && (qo16 & 1), o16 = packed && (qo16 & 2), qp = q16 && (qo16 & 4) && K <= 32;
-            static const int vfuse_env = getenv("MSSVT_ATTN_VFUSE") ? atoi(getenv("MSSVT_ATTN_VFUSE")) : 0;
-            const bool vfuse = (vfuse_env == 1 || vfuse_env == 2) && qp && o16 && HP * HD == CG;  // V formed in the window launch (round 6)
-            if constexpr (HD == 16 && !KVH_QT_AHEAD) {
+            // packed weights: A and C as k_attn_q16 / k_attn_o16, and at K <= 32 the Q' hand-off (Qt formed in the window launch)
+            const bool qp = packed && K <= 32;
+            if constexpr (HD == 16) {
                 if (qp) {
                     using L = AttnBlob<CG>;
                     const dim3 qp_grid(cus * 3 / ng > 0 ? cus * 3 / ng : 1, ng);
                     k_attn_q16<CG, HP, 2><<<dim3(grid16, ng), ATTN_QO16_WAVES * MSSVT_WAVE, L::WK + CG * 4, stream>>>(pack);
-                    if constexpr (HP * HD == CG) {
-#define KVH_V_LAUNCH(VOUT_, NWV_)                                                                                              \
-    {                                                                                                                          \
-        const size_t lds_v = (size_t)((VOUT_ ? L::BYTES : L::WV2) - L::WK2) + (size_t)(NWV_) * 2 * 2 * 16 * RS;               \
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_attn_kvh<CG, HD, HP, 2, true, VOUT_, NWV_>),       \
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_v);                           \
-        if (e != hipSuccess) return (int)e;                                                                                    \
-        const int per_cu = 12 / (NWV_);                                                                                        \
-        const dim3 v_grid(cus * per_cu / ng > 0 ? cus * per_cu / ng : 1, ng);                                                  \
-        k_attn_kvh<CG, HD, HP, 2, true, VOUT_, NWV_><<<v_grid, (NWV_) * MSSVT_WAVE, lds_v, stream>>>(pack);                    \
-    }
-                        // V hand-off (experiments): 1 = one 12-wave workgroup per CU and group half (the
-                        // fragments are shared), 2 = 4-wave workgroups (68 KB each: two per CU), 3 = X-bar hand-off on 12-wave workgroups
-                        if (vfuse && vfuse_env == 1) KVH_V_LAUNCH(true, 12)
-                        else if (vfuse && vfuse_env == 2) KVH_V_LAUNCH(true, 4)
-                        else if (vfuse_env == 3) KVH_V_LAUNCH(false, 12)
-#undef KVH_V_LAUNCH
-                    }
-                    if (!((vfuse || vfuse_env == 3) && HP * HD == CG))
-                        k_attn_kvh<CG, HD, HP, 2, true><<<qp_grid, ATTN_ROW_WAVES * MSSVT_WAVE, (L::WV2 - L::WK2) + 2 * img, stream>>>(pack);
+                    k_attn_kvh<CG, HD, HP, 2, true><<<qp_grid, ATTN_ROW_WAVES * MSSVT_WAVE, (L::WV2 - L::WK2) + 2 * img, stream>>>(pack);
                 }
             }
             if constexpr (HD == 16) {
-                if (q16 && !qp)
+                if (packed && !qp)
                     k_attn_q16<CG, HP, 1><<<dim3(grid16, ng), ATTN_QO16_WAVES * MSSVT_WAVE, AttnBlob<CG>::WV + CG * 4, stream>>>(pack);
             }
-            if (!q16)
+            if (!packed)
                 k_attn_q<CG, HD, HP, true><<<dim3(row_grid, ng), ATTN_QO_WAVES * MSSVT_WAVE, lds_q, stream>>>(pack);
             if (qp) {
             } else if (K <= 32)
@@ -1469,12 +1343,10 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
                 k_attn_kvh<CG, HD, HP, 4, false><<<kv_grid, ATTN_ROW_WAVES * MSSVT_WAVE, 4 * img, stream>>>(pack);
             }
             if constexpr (HD == 16) {
-                if (o16 && vfuse)
-                    k_attn_o16<CG, HP, true><<<dim3(grid16, ng), ATTN_QO16_WAVES * MSSVT_WAVE, AttnBlob<CG>::WK2 - AttnBlob<CG>::WV + 2 * CG * 4, stream>>>(pack);
-                else if (o16)
+                if (packed)
                     k_attn_o16<CG, HP><<<dim3(grid16, ng), ATTN_QO16_WAVES * MSSVT_WAVE, AttnBlob<CG>::WK2 - AttnBlob<CG>::WV + 2 * CG * 4, stream>>>(pack);
             }
-            if (!o16)
+            if (!packed)
                 k_attn_o<CG, HD, HP><<<dim3(row_grid, ng), ATTN_QO_WAVES * MSSVT_WAVE, lds_o, stream>>>(pack);
             return mssvt_launch_status();
         }
@@ -1487,8 +1359,7 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
     // window without a work list (the ~37 k empty workgroups of a capacity-sized grid cost 5 k cycles each: 92 us), and
     // the same pipeline squeezed under 128 VGPRs for 4 waves / SIMD (18 spilled registers, 63 us): per window the SIMD
     // is busy ~3.2 k of the wave's 9.7 k cycles, more than half of it fp32 matrix instructions -- not a latency problem.
-    static const int kv_wgs = getenv("MSSVT_ATTN_KV_WGS") ? atoi(getenv("MSSVT_ATTN_KV_WGS")) : 3;
-    const dim3 kv_grid(cus * kv_wgs / ng > 0 ? cus * kv_wgs / ng : 1, ng);
+    const dim3 kv_grid(cus * 3 / ng > 0 ? cus * 3 / ng : 1, ng);
     const size_t lds_tile = (size_t)ATTN_ROW_WAVES * 16 * LS * 4;  // per key tile of 16 slots, all waves
     if (K <= 16)
         k_attn_kv<CG, HD, HP, 1><<<kv_grid, ATTN_ROW_WAVES * MSSVT_WAVE, lds_tile, stream>>>(pack);
@@ -1566,7 +1437,6 @@ static int block_attention_impl(
         a.attn = attn;
         a.row_capacity = row_capacity;
         a.packed = host_packed ? host_packed[g] : nullptr;
-        a.xcd = mssvt_xcd_remap();
         qoff += (size_t)row_capacity * (((heads + 3) / 4) * 4) * Cg;
         if (same) {
             pack.g[g] = a;

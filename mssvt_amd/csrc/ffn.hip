@@ -38,8 +38,6 @@ struct FfnArgs {
     const float *ln2_w, *ln2_b;  // optional second LayerNorm applied to y (next block's norm1)
     float eps2;
     float *y_norm;
-    int xcd;  // deal the tiles so that an XCD owns a contiguous run per round (common.hip.h, xcd_contiguous_block)
-    int prio;
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -612,9 +610,9 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
     // voxels of a window lie in three x-slabs ~160 rows apart in the (b, x, y, z) order and gather the SAME attention rows, so
     // the rows a workgroup gathers were mostly fetched into ITS XCD's L2 by a neighbour a moment ago.  Round-robin tiles put
     // consecutive tiles on different XCDs (each with an L2 of its own): 146 MB of HBM traffic per launch against 114 MB
-    // algorithmic.  MSSVT_XCD_REMAP=0 restores the round-robin deal.
+    // algorithmic.
     int tstep = gridDim.x, tend = tiles, tile0 = blockIdx.x;
-    if (a.xcd && (gridDim.x & 7) == 0 && tiles >= 8 * (int)gridDim.x) {
+    if ((gridDim.x & 7) == 0 && tiles >= 8 * (int)gridDim.x) {
         const int x = blockIdx.x & 7, per_xcd = (tiles + 7) >> 3;
         tstep = gridDim.x >> 3;
         tile0 = x * per_xcd + (int)(blockIdx.x >> 3);
@@ -810,8 +808,8 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
     // every vector instruction: both waves of a SIMD then want the same pipe at the same time) or hoists every LDS read to
     // the top (spills at 256 registers); sched_group_barrier patterns were tried and are not stable from build to build.
     // the later-dispatched half of the workgroup -- the loser of every issue arbitration on its SIMD, MI355X_MICROARCH.md "Two
-    // waves per SIMD" item 4 -- runs at static priority 1: 46.4 -> 46.0 and 47.4 -> 46.5 us on two boxes (MSSVT_FFN_PRIO=0: off)
-    if (a.prio && wv >= NW / 2) __builtin_amdgcn_s_setprio(1);
+    // waves per SIMD" item 4 -- runs at static priority 1: 46.4 -> 46.0 and 47.4 -> 46.5 us on two boxes
+    if (wv >= NW / 2) __builtin_amdgcn_s_setprio(1);
     for (;;) {
         const int tile_next = tile + tstep;
         const bool has_next = tile_next < tend;
@@ -1074,7 +1072,7 @@ extern "C" int mssvt_ffn_fused(int n_rows, int C, int FF, const float *x_new, co
     a.tab_row = nullptr; a.tab_w = nullptr; a.attn = nullptr;
     a.ln_w = norm_w; a.ln_b = norm_b; a.eps = eps;
     a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.y = y;
-    a.ln2_w = next_norm_w; a.ln2_b = next_norm_b; a.eps2 = next_eps; a.y_norm = y_norm; a.xcd = mssvt_xcd_remap(); a.prio = getenv("MSSVT_FFN_PRIO") ? atoi(getenv("MSSVT_FFN_PRIO")) : 1;
+    a.ln2_w = next_norm_w; a.ln2_b = next_norm_b; a.eps2 = next_eps; a.y_norm = y_norm;
     return dispatch_ffn(C, FF, a, hidden, phases, (hipStream_t)stream);
 }
 
@@ -1100,6 +1098,6 @@ extern "C" int mssvt_ffn_fused_interp(int n_rows, int C, int FF, const float *x_
     a.attn = attn;
     a.ln_w = norm_w; a.ln_b = norm_b; a.eps = eps;
     a.W1 = W1; a.b1 = b1; a.W2 = W2; a.b2 = b2; a.y = y;
-    a.ln2_w = next_norm_w; a.ln2_b = next_norm_b; a.eps2 = next_eps; a.y_norm = y_norm; a.xcd = mssvt_xcd_remap(); a.prio = getenv("MSSVT_FFN_PRIO") ? atoi(getenv("MSSVT_FFN_PRIO")) : 1;
+    a.ln2_w = next_norm_w; a.ln2_b = next_norm_b; a.eps2 = next_eps; a.y_norm = y_norm;
     return dispatch_ffn(C, FF, a, hidden, phases, (hipStream_t)stream);
 }

@@ -39,7 +39,7 @@ typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
 #define PS_MFMA(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
 #define PS_FIX 1048576.0  // 2^20 steps per metre (csrc/vfe.hip)
 #define PS_SCAN 1024      // counts per scan block
-#define PS_TASK_DEFAULT 16  // sorted rows per task window of k_ps_pfn2 (MSSVT_PFN_TASK = 16 | 32 | 64: 37.3 / 45.9 / 45.1 us at 160k points)
+#define PS_TASK_DEFAULT 16  // sorted rows per task window of k_ps_pfn2 (16 | 32 | 64: 37.3 / 45.9 / 45.1 us at 160k points)
 
 __global__ void __launch_bounds__(256) k_ps_rank(const int *voxel, long long P, int *count, int *slot) {
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -465,8 +465,7 @@ extern "C" int mssvt_pfn_sorted_64_128(const float *points, int point_stride, lo
     k_ps_rank<<<divup(num_points, 256), 256, 0, stream>>>(point_voxel, num_points, count, slot);
     k_ps_scan1<<<nb, 256, 0, stream>>>(count, N, local, block_sum);
     k_ps_scan2<<<1, 1024, 0, stream>>>(block_sum, nb, total);
-    static const int task_env = getenv("MSSVT_PFN_TASK") ? atoi(getenv("MSSVT_PFN_TASK")) : 0;
-    const int task_rows = task_env == 16 || task_env == 32 || task_env == 64 ? task_env : PS_TASK_DEFAULT;
+    const int task_rows = PS_TASK_DEFAULT;
     const long long nthreads = num_points > N + 1 ? num_points : N + 1;
     k_ps_place<<<divup(nthreads, 256), 256, 0, stream>>>(point_voxel, num_points, slot, local, block_sum, total, N, task_rows, points,
                                                          point_stride, pts8, row_voxel, start, out);

@@ -19,7 +19,6 @@
 //
 // The number of windows is read from DEVICE memory (no host round trip); the grid
 // is sized for the capacity and surplus waves exit.
-#include <stdlib.h>
 #include "common.hip.h"
 #define PLAN_MAX_WPB 4
 #ifndef PLAN_WAVES_PER_SIMD
@@ -783,7 +782,6 @@ extern "C" int mssvt_window_plan_two(
             wpb = cand;
         }
     }
-    if (getenv("MSSVT_PLAN_WPB")) wpb = atoi(getenv("MSSVT_PLAN_WPB"));
     const size_t lds_bytes = (size_t)a.lds_words_per_wave * 4 * wpb;
     if (lds_bytes > 160 * 1024) return MSSVT_E_TOOLARGE;
     // lists of 512 .. 1023 / 1024 .. 2047 slots: the instantiations with the 8- / 16-slot register samplers

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fill the @PLACEHOLDER@ numbers of DESIGN.md / README.md from profiles/<tag>_* (tools/collect_profiles_r05.sh): python tools/fill_docs.py r05_b"""
+"""Fill the @PLACEHOLDER@ numbers of DESIGN.md / README.md from profiles/<tag>_* (bench lines and training profiles of one GPU pass): python tools/fill_docs.py r05_b"""
 import csv
 import json
 import os
