@@ -9,9 +9,5 @@ def use_device_kernargs():
     link -- 0.80 -> 0.76 ms per frame on one box (bench.py, configs[1]).  The runtime reads the variable when HIP
     initialises, so this must run before the first GPU call of the PROCESS; it changes the environment of the host
     application and of its children, which is why importing the package does not do it: bench.py and the tools call it,
-    an application opts in here or with MSSVT_DEV_KERNARG=1.  An explicit HIP_FORCE_DEV_KERNARG in the environment wins."""
+    an application opts in here.  An explicit HIP_FORCE_DEV_KERNARG in the environment wins."""
     _os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
-
-
-if _os.environ.get("MSSVT_DEV_KERNARG", "0") == "1":
-    use_device_kernargs()

@@ -13,7 +13,6 @@ per-voxel max a ``scatter_reduce('amax')`` (gradient to the maximal rows; pinned
 module by tests/golden/dynamic_vfe_train_*.npz: output, every parameter gradient, the BatchNorm buffers).
 """
 import ctypes
-import os
 
 import torch
 from torch import nn
@@ -21,10 +20,10 @@ from torch import nn
 from . import _lib, voxelize
 
 _i = ctypes.c_int
-FUSED_PFN = os.environ.get("MSSVT_FUSED_PFN", "1") != "0"  # csrc/pfn_fused.hip for the default DynamicVFE configuration
-# ... over points grouped by voxel (csrc/pfn_sorted.hip: no atomics on feature rows, no fills, x2 never stored); "0": the
-# atomic reductions of round 5 (kept: the comparator of tests/test_vfe_gpu.py)
-SORTED_PFN = os.environ.get("MSSVT_PFN_SORTED", "1") != "0"
+# the fused PFN of the default DynamicVFE configuration (csrc/pfn_fused.hip) over points grouped by voxel (csrc/pfn_sorted.hip:
+# no atomics on feature rows, no fills, x2 never stored); False: the atomic reductions of round 5 (kept: the comparator of
+# tests/test_vfe_gpu.py)
+SORTED_PFN = True
 
 
 def voxel_mean_xyz(points, point_voxel, num_voxels):
@@ -134,7 +133,7 @@ class DynamicVFE(nn.Module):
 
     def _fused_pfn_ok(self, points):
         """The two PFN layers as two HIP launches (csrc/pfn_fused.hip): the default configuration only."""
-        if not FUSED_PFN or self.num_point_features_in != 5 or not self.with_cluster_center or not self.with_voxel_center or \
+        if self.num_point_features_in != 5 or not self.with_cluster_center or not self.with_voxel_center or \
                 self.with_distance or len(self.pfn) != 2 or points.dtype != torch.float32 or points.shape[1] < 6:
             return False
         shapes = [(blk[0].in_features, blk[0].out_features) for blk in self.pfn]

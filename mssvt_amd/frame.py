@@ -13,19 +13,19 @@ ref: MixedScaleSparseTransformer.forward, pcdet/models/backbones_3d/mssvt_backbo
 """
 import ctypes
 import logging
-import os
 
 import torch
 
 from . import _lib, fused, mssvt_ops
 from .mssvt_utils import SparseTensor
 
-ENABLED = os.environ.get("MSSVT_FRAME", "1") != "0"
+ENABLED = True  # False: every frame takes the Python-driven path of fused.py
 _WORDS = 192
-# the first norm1 on a second stream, under the Blocks' plan kernel (the pillar lists come out of the level set-up): "auto" = from
-# OVERLAP_MIN_VOXELS up (measured with the frame call: one scene 1 432 -> 1 422 frames/s, batch 4 1 739 -> 1 782, batch 8
-# 1 828 -> 1 853: the plan kernel slows down when it shares the chip, large frames gain more than that costs)
-OVERLAP = os.environ.get("MSSVT_FRAME_OVERLAP", "auto")
+# the first norm1 on a second stream, under the Blocks' plan kernel (the pillar lists come out of the level set-up): "1" / "0" =
+# always / never, "auto" = from OVERLAP_MIN_VOXELS up (measured with the frame call: one scene 1 432 -> 1 422 frames/s,
+# batch 4 1 739 -> 1 782, batch 8 1 828 -> 1 853: the plan kernel slows down when it shares the chip, large frames gain more
+# than that costs)
+OVERLAP = "auto"
 OVERLAP_MIN_VOXELS = 250000
 
 
@@ -260,9 +260,9 @@ def forward(net, feats, coords, batch_size, defer=False):
     fused.UnsortedVoxels when the voxel list is not (b,x,y,z)-sorted (the caller redoes the frame order-agnostically).
     `defer`: return a `Pending` right behind the enqueue instead -- its `finish()` does the frame's one host wait
     (mssvt_amd/pipeline.py keeps several frames in flight that way without the host standing still in between)."""
-    if not ENABLED or torch.is_grad_enabled() or fused.FFN_TIMER is not None or net.async_index:
+    if not ENABLED or torch.is_grad_enabled() or fused.FFN_TIMER is not None:
         return None
-    if not (fused.SORTED_LEVELS and fused.OCC_COLUMNS and fused.PLAN_TABLES and fused.CMP_FUSED and fused.LEVEL_SETUP):
+    if not (fused.SORTED_LEVELS and fused.OCC_COLUMNS):
         return None
     if not (feats.is_cuda and feats.dtype == torch.float32 and feats.dim() == 2 and feats.is_contiguous()):
         return None

@@ -62,7 +62,7 @@ ATTN_SHAPES = {(8, 8), (16, 8), (16, 16), (24, 8), (32, 8), (32, 16), (32, 32), 
                (64, 32)}
 
 
-TRAIN_COMPACT = os.environ.get("MSSVT_TRAIN_COMPACT", "1") != "0"  # 0: training through the padded operator path
+TRAIN_COMPACT = True  # False: training through the padded operator path
 
 
 def _needs_grad(block, sp):
@@ -123,7 +123,7 @@ def level_state(sp, blocks=()):
 # Levels whose voxel list is sorted by (b, x, y, z) -- what DynamicVFE / the device voxelizer emit -- are set up from
 # one occupancy bitmap (csrc/level_sorted.hip): no voxel hash table, no insert-min / rank passes, no counting atomics.
 # The device verifies the order; a list in any other order takes the order-agnostic kernels (mssvt_level_setup).
-SORTED_LEVELS = os.environ.get("MSSVT_SORTED_LEVELS", "1") != "0"
+SORTED_LEVELS = True
 
 
 class UnsortedVoxels(Exception):
@@ -237,9 +237,6 @@ def _pinned_words(owner, n, dev):
     return t
 
 
-PARTITION_GROUPS = True  # a Block's window partition and the next CompressBlock's share their launches
-
-
 def _partition_key(block):
     return (tuple(int(v) for v in block.win1_size), int(block.max_num_wins))
 
@@ -254,8 +251,7 @@ def window_partition(block, sp, st, need_table=False):
     if key not in parts or (need_table and parts[key][1] is None):
         todo = [block]
         nxt = getattr(sp, "_next_compress", None)
-        if (PARTITION_GROUPS and nxt is not None and nxt is not block and _partition_key(nxt) not in parts
-                and _partition_key(nxt) != key):
+        if nxt is not None and nxt is not block and _partition_key(nxt) not in parts and _partition_key(nxt) != key:
             todo.append(nxt)
         shapes = [[sp.spatial_shape[i] // b.win1_size[i] for i in range(3)] for b in todo]
         res = mssvt_ops.window_partitions_device([b.win1_size for b in todo], [b.max_num_wins for b in todo],
@@ -263,9 +259,6 @@ def window_partition(block, sp, st, need_table=False):
         for b, r in zip(todo, res):
             parts[_partition_key(b)] = r
     return parts[key]
-
-
-LEVEL_SETUP = True  # counts + voxel table + occupancy columns + window partitions of the input level in one call
 
 
 @_no_grad
@@ -277,7 +270,7 @@ def setup_input_level(blocks, sp_kwargs, assume_sorted=True):
     from .mssvt_backbone import MixedScaleSparseTransformerCompressBlock as Compress
     indices = sp_kwargs["indices"]
     n = indices.shape[0]
-    if not (LEVEL_SETUP and indices.is_cuda and n > 0 and indices.dtype == torch.int32 and indices.is_contiguous()):
+    if not (indices.is_cuda and n > 0 and indices.dtype == torch.int32 and indices.is_contiguous()):
         return None
     dev = indices.device
     B, H = int(sp_kwargs["batch_size"]), int(sp_kwargs["hash_size"])
@@ -338,9 +331,6 @@ def occupancy_columns(sp, st):
     return st["occ"]
 
 
-PLAN_TABLES = os.environ.get("MSSVT_PLAN_TABLES", "1") != "0"
-
-
 def _lists_disjoint(block):
     """True when the win1 lists (hence the odd / even lists) of different windows cannot share a voxel: every offset of
     the three tables inside the window's own cells.  Then each listed voxel is owned by its window and the plan kernel
@@ -361,7 +351,7 @@ def _plan_tables(block, sp, p, key, dev, N):
     none = (_i(0), None, None, None, None, None)
     p.tables = {}
     group = [b for b in (getattr(sp, "_plan_group", None) or [block]) if b.plan_key() == key and supported(b, sp)]
-    if not PLAN_TABLES or not group or not _lists_disjoint(block):
+    if not group or not _lists_disjoint(block):
         return none, []
     todo, seen = [], set()
     for b in group:
@@ -611,10 +601,11 @@ def _attn_refs(block, groups):
 
 # launch B of the fp32 attention (scores, softmax, weighted key sum per window) with split-fp16 matrix operands
 # (csrc/block_attn.hip, k_attn_kvh: hi + 2^-11 lo halves, 3 x v_mfma_f32_16x16x32_f16 per product sum, fp32 accumulation --
-# the FFN's arithmetic); "0" keeps the fp32 matrix instruction.  Operands outside the fp16 range always take the fp32 form.
-ATTN_KV16 = os.environ.get("MSSVT_ATTN_KV16", "1") != "0"
-# ... and the two row-tiled launches on pre-split weight fragments (k_attn_q16 / k_attn_o16); "0": fp32 matrix instruction
-ATTN_QO16 = os.environ.get("MSSVT_ATTN_QO16", "1") != "0"
+# the FFN's arithmetic); False keeps the fp32 matrix instruction.  Operands outside the fp16 range always take the fp32 form.
+# `blk.attn_kv16` / `blk.attn_qo16` override the two per Block.
+ATTN_KV16 = True
+# ... and the two row-tiled launches on pre-split weight fragments (k_attn_q16 / k_attn_o16); False: fp32 matrix instruction
+ATTN_QO16 = True
 
 
 @_no_grad
@@ -688,15 +679,14 @@ def _attention_call(block, p, od, C, nq, xhat, qbuf, attn, groups=None):
 
 
 FFN_SHAPES = {(128, 256), (64, 128), (32, 64)}  # instantiated in csrc/ffn.hip
-CMP_FUSED = os.environ.get("MSSVT_CMP_FUSED", "1") != "0"
 FFN_TIMER = None  # bench.py sets this to a list to time k_ffn_up live (see _ffn_tail)
 # arithmetic of the FFN's matrix products: "f16x3" = every fp32 operand split into two fp16 halves (hi + 2^-11 lo: 22 of 24 mantissa bits), three
 # 16-bit MFMAs per product sum, fp32 accumulation (k_ffn_ws: same error against float64 as the fp32 instruction, 3/16 of
 # its cycles, one launch); "f32" = v_mfma_f32_16x16x4_f32 (k_ffn_up + k_ffn_down).  A module attribute `ffn_arith`
 # overrides it; operands outside the fp16 range (checked from the parameters) always take "f32".
-FFN_ARITH = os.environ.get("MSSVT_FFN_ARITH", "f16x3")
+FFN_ARITH = "f16x3"
 FFN_F16_LIMIT = 6.0e4  # fp16 max = 65504; the conversions round toward zero (never to inf)
-OCC_COLUMNS = os.environ.get("MSSVT_OCC_COLUMNS", "1") != "0"
+OCC_COLUMNS = True
 
 
 def _ffn_refs(block):
@@ -710,11 +700,11 @@ def _ffn_refs(block):
     return r
 
 
-VERIFY_WEIGHTS = os.environ.get("MSSVT_VERIFY_WEIGHTS", "0") == "1"
+VERIFY_WEIGHTS = False
 
 
 def _content_key(ts):
-    """Debug mode (MSSVT_VERIFY_WEIGHTS=1): a checksum of the parameter CONTENTS joins the cache keys, so that even a write
+    """Debug mode (VERIFY_WEIGHTS = True): a checksum of the parameter CONTENTS joins the cache keys, so that even a write
     through `.data` (which leaves `_version` alone) is noticed -- at one host sync per call."""
     if not VERIFY_WEIGHTS:
         return ()
@@ -836,17 +826,8 @@ def layer_norm(x, norm):
 
 
 # ---------------------------------------------------------------------------------------------------------
-# Index work of a frame on a second HIP stream (MixedScaleSparseTransformer.async_index)
+# Two launches of a frame on a second HIP stream (overlap_front)
 # ---------------------------------------------------------------------------------------------------------
-# Everything a resolution level needs before its first feature kernel -- sample counts, voxel hash table, occupancy
-# columns, window partitions, the two-scale plan (K3 + 2 x FPS + masks + metadata), work orders, interpolation tables, the
-# CompressBlock's plan -- depends on the voxel INDICES only: integer / VALU / latency bound work, ~25 % of a frame's GPU
-# time, while the feature kernels are HBM / matrix bound.  With `async_index` the forward issues it on a side stream and
-# the feature kernels on the caller's stream behind one event; the next frame's index work then runs UNDER this frame's
-# feature kernels (the host is one frame ahead anyway: the forward's only host wait is an early device-to-host copy of
-# the window count).  Buffers allocated on the side stream and read by the feature kernels are handed to the caching
-# allocator with `record_stream`, so that a buffer freed by the host is not reused by the next frame's index work
-# while this frame's feature kernels still read it.
 _side_streams = {}
 
 
@@ -859,19 +840,19 @@ def side_stream(dev):
     return s
 
 
-# A lighter form of the same idea: only the two launches of a frame that neither need nor feed the index
-# chain -- the first Block's LayerNorm (HBM bound, 16 us) and the CompressBlock's pillar plan (one lane per window, 10 us
-# + its prefill) -- go to the side stream, under the Blocks' plan kernel (VALU / latency bound, 70 us).  Two events, no
-# record_stream walk: the side stream starts every frame behind everything queued on the caller's stream
-# (wait_stream), so memory it allocates is never rewritten before its readers are done.
+# Only the two launches of a frame that neither need nor feed the index chain -- the first Block's LayerNorm (HBM bound,
+# 16 us) and the CompressBlock's pillar plan (one lane per window, 10 us + its prefill) -- go to the side stream, under
+# the Blocks' plan kernel (VALU / latency bound, 70 us).  Two events, no record_stream: the side stream starts every frame
+# behind everything queued on the caller's stream (wait_stream), so memory it allocates is never rewritten before its
+# readers are done.
 # Measured (bench.py, one box each): one scene 0.73 -> 0.80 ms with it (the cross-stream waits and the two stream switches
-# cost more than the 26 us they hide), batch 4 (297k voxels) 2.407 -> 2.420 ms, batch 8 (594k) / bf16 4.15 -> 4.09 ms.  "auto": on from SIDE_OVERLAP_MIN_VOXELS up.
-SIDE_OVERLAP = os.environ.get("MSSVT_SIDE_OVERLAP", "auto")
+# cost more than the 26 us they hide), batch 4 (297k voxels) 2.407 -> 2.420 ms, batch 8 (594k) / bf16 4.15 -> 4.09 ms: on
+# from SIDE_OVERLAP_MIN_VOXELS up.
 SIDE_OVERLAP_MIN_VOXELS = 400000
 
 
 def side_overlap_on(sp):
-    return SIDE_OVERLAP == "1" or (SIDE_OVERLAP == "auto" and sp.features.shape[0] >= SIDE_OVERLAP_MIN_VOXELS)
+    return sp.features.shape[0] >= SIDE_OVERLAP_MIN_VOXELS
 
 
 @_no_grad
@@ -893,7 +874,7 @@ def overlap_front(schedule, sp):
         sp._xhat, sp._xhat_event = (xhat, blk.norm1, sp.features), ev
         C = sp.features.shape[1]
         if cmp_blk is not None and getattr(cmp_blk, "impl", None) == "fused" and getattr(sp, "_level", None) is not None and \
-                sp._level.get("sorted") and compress_supported(cmp_blk, sp) and CMP_FUSED and \
+                sp._level.get("sorted") and compress_supported(cmp_blk, sp) and \
                 cmp_blk.linear1.in_features == C and _compress_fused_ok(cmp_blk, sp, C):
             sp._cmp_plan = (cmp_blk, one_scale_plan(cmp_blk, sp, sync=False))
             ev2 = torch.cuda.Event()
@@ -905,52 +886,6 @@ def _wait_side(sp, name):
     ev = sp.__dict__.pop(name, None)
     if ev is not None:
         torch.cuda.current_stream(sp.features.device).wait_event(ev)
-
-
-@_no_grad
-def prefetch_level(schedule, sp):
-    """All index work of the input level, on the CURRENT stream: the plans of its Blocks (with their work orders and
-    interpolation tables) and the plan of the CompressBlock that ends it.  The feature phase finds them cached."""
-    from .mssvt_backbone import MixedScaleSparseTransformerCompressBlock as Compress
-    done = set()
-    for blk, _nxt_norm, group, nxt_cmp in schedule:
-        if getattr(blk, "impl", None) != "fused":
-            break
-        if isinstance(blk, Compress):
-            C = sp.features.shape[1]
-            if compress_supported(blk, sp) and CMP_FUSED and blk.linear1.in_features == C and _compress_fused_ok(blk, sp, C):
-                sp._cmp_plan = (blk, one_scale_plan(blk, sp, sync=False))
-            break
-        if not supported(blk, sp) or blk.linear1.in_features != sp.features.shape[1] or hasattr(blk, "out_linear"):
-            break
-        k = blk.plan_key()
-        if k in done:
-            continue
-        done.add(k)
-        sp._plan_group, sp._next_compress = group, nxt_cmp
-        p = two_scale_plan(blk, sp)
-        if group and not getattr(p, "group_done", False):
-            p.group_done = True
-            prepare_group([b for b in group if b.plan_key() == k and supported(b, sp)], sp, p)
-
-
-def record_streams(roots, stream):
-    """`record_stream(stream)` on every device tensor reachable from `roots` (plans, level state, arena)."""
-    seen, stack = set(), list(roots)
-    while stack:
-        o = stack.pop()
-        if o is None or id(o) in seen:
-            continue
-        seen.add(id(o))
-        if torch.is_tensor(o):
-            if o.is_cuda:
-                o.record_stream(stream)
-        elif isinstance(o, dict):
-            stack.extend(o.values())
-        elif isinstance(o, (list, tuple)):
-            stack.extend(o)
-        elif isinstance(o, _Plan) or type(o).__name__ in ("SparseTensor", "FillArena"):
-            stack.extend(o.__dict__.values())
 
 
 def block_forward(block, sp):
@@ -1300,7 +1235,7 @@ def _compress_f16_ok(block, sp):
     return cache["ok"]
 
 
-CMP_WS = os.environ.get("MSSVT_CMP_WS", "1") != "0"  # csrc/compress_ws.hip (sorted pillar levels); 0: compress_fused.hip
+CMP_WS = True  # csrc/compress_ws.hip (sorted pillar levels); False: compress_fused.hip
 
 
 @_no_grad
@@ -1368,7 +1303,7 @@ def _compress_forward_fused(block, sp, xhat, x_in):
     (the output shape)."""
     C = x_in.shape[1]
     dev = x_in.device
-    pre = sp.__dict__.pop("_cmp_plan", None)  # built ahead on the index stream (prefetch_level / overlap_front)
+    pre = sp.__dict__.pop("_cmp_plan", None)  # built ahead on the side stream (overlap_front)
     _wait_side(sp, "_cmp_plan_event")
     p = pre[1] if pre is not None and pre[0] is block else one_scale_plan(block, sp, sync=False)
     if not p.disjoint or p.with_pad:
@@ -1434,7 +1369,7 @@ def compress_forward(block, sp):
     x_in = sp.features.contiguous()
     C = x_in.shape[1]
     dev = x_in.device
-    if CMP_FUSED and _compress_fused_ok(block, sp, C):
+    if _compress_fused_ok(block, sp, C):
         y, p = _compress_forward_fused(block, sp, xhat, x_in)
         if y is not None:
             return _compress_finish(sp, p, y)

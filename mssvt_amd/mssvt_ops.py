@@ -14,7 +14,6 @@ All work happens in libmssvt_hip.so (hand-written HIP, include/mssvt_hip.h);
 there is no CPU fallback.
 """
 import ctypes
-import os
 
 import torch
 
@@ -24,7 +23,7 @@ ST_DUPLICATE_KEY, ST_TABLE_OVERFLOW, ST_WINDOW_OVERFLOW, ST_UNSORTED = 1, 2, 4, 
 
 # The reference asserts ``features.shape[0] == features_batch_cnt.sum()`` (mssvt_ops.py:157-160),
 # which costs two host syncs per call; here those checks are opt-in.
-CHECK_COUNTS = os.environ.get("MSSVT_CHECK_COUNTS", "0") == "1"
+CHECK_COUNTS = False
 
 _i = ctypes.c_int
 

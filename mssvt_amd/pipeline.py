@@ -18,8 +18,9 @@ hardware interleaves their kernels.  Every frame computes exactly what `net(batc
 The reference runs its frames one by one on the legacy default stream ("Threading / streams"); this is the
 MI355X-side answer to the same loop (a detector's data loader hands over frame i + 1 while frame i is still running).
 
-Which streams (`STREAMS`, or MSSVT_PIPE_STREAMS=cumask|priority|pooled).  Measured on one MI355X, one 160k-point scene per
-step, four frames in flight (one frame at a time: 1 555 - 1 575 frames/s; profiles/r06_*_two_streams.txt, r06_*_pipe_trace.txt):
+Which streams (`STREAMS`: "cumask" or "pooled"; `priority` was measured and not kept).  Measured on one MI355X, one
+160k-point scene per step, four frames in flight (one frame at a time: 1 555 - 1 575 frames/s; profiles/r06_*_two_streams.txt,
+r06_*_pipe_trace.txt):
 
                                              bench.py loop, 20 / 50 steps      + a consumer kernel per frame on the DEFAULT / a side stream
     cumask    (own hardware queue each)          1 680 / 1 784                      592 / 1 646     (100-step loop: 1 878)
@@ -39,7 +40,7 @@ step, four frames in flight (one frame at a time: 1 555 - 1 575 frames/s; profil
   (the implicit ordering already covers them), and the default call runs at the deferred rate (1 552 / 1 850 at depth 1 / 4).
   What remains is the consumer side: kernels a caller launches on the DEFAULT stream join every frame in flight (592 frames/s).
   Run the stages around the backbone on a side stream (`with torch.cuda.stream(side):` -- 1 646), inside the pipeline
-  (`FramePipeline(chain)`), or select `priority` / `pooled` streams (no legacy coupling, 1 6xx - 1 7xx either way); `get()`
+  (`FramePipeline(chain)`), or set `pipeline.STREAMS = "pooled"` (no legacy coupling, 1 746 / 1 749); `get()`
   logs a warning once when it is called with the default stream current on `cumask` streams.
 * A consumer waits for ITS frame (an event recorded right behind the frame), not for the frame's stream: `wait_stream`
   would also wait for the next frame already queued there, and the next submission would wait for the consumer -- the
@@ -47,12 +48,11 @@ step, four frames in flight (one frame at a time: 1 555 - 1 575 frames/s; profil
 """
 import ctypes
 import logging
-import os
 
 import torch
 
 
-STREAMS = "cumask"  # "cumask": a hardware queue of its own per stream (blocking w.r.t. the default stream); "priority"; "pooled"
+STREAMS = "cumask"  # "cumask": a hardware queue of its own per stream (blocking w.r.t. the default stream); "pooled"
 
 
 def auto_depth(batch_size):
@@ -122,13 +122,11 @@ class FramePipeline(object):
         self.net = net  # the backbone, or any callable batch_dict -> batch_dict (then pass `device`)
         self.pre, self.post = pre, post
         self.device = torch.device(device if device is not None else next(net.parameters()).device)
-        kind = os.environ.get("MSSVT_PIPE_STREAMS", "pooled" if os.environ.get("MSSVT_PIPE_POOLED") == "1" else STREAMS)
-        self.streams = _own_queue_streams(depth, self.device) if kind == "cumask" else None
+        self.streams = _own_queue_streams(depth, self.device) if STREAMS == "cumask" else None
         self.own_queues = self.streams is not None  # (blocking streams in the legacy sense: module docstring)
         if self.streams is None:
-            prio = -1 if kind == "priority" else 0
-            self.streams = [torch.cuda.Stream(self.device, priority=prio) for _ in range(depth)]
-        self.stream_kind = "cumask" if self.own_queues else ("priority" if kind == "priority" else "pooled")
+            self.streams = [torch.cuda.Stream(self.device) for _ in range(depth)]
+        self.stream_kind = "cumask" if self.own_queues else "pooled"
         self.turn = 0
         self.frame_events = True
         self.pending = [None] * depth  # per stream: the frame whose host wait has not happened yet
@@ -282,7 +280,7 @@ class PendingFrame(object):
                     self.pipe._warned = True
                     logging.getLogger("mssvt_amd.pipeline").warning(
                         "FramePipeline: the consumer runs on the legacy default stream, which joins every frame in flight on the "
-                        "pipeline's (blocking) streams -- run it under torch.cuda.stream(side) or set MSSVT_PIPE_STREAMS=priority")
+                        "pipeline's (blocking) streams -- run it under torch.cuda.stream(side) or set pipeline.STREAMS = \"pooled\"")
                 if self.done is not None:
                     cur.wait_event(self.done)
                 else:

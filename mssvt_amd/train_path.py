@@ -18,7 +18,6 @@ Same arithmetic as the reference up to re-association: masked key slots (additiv
 and empty query slots are dropped instead of padded; the interpolation uses the plan's 3-NN table (weights are geometry only).
 """
 import ctypes
-import os
 
 import torch
 import torch.nn.functional as F
@@ -344,7 +343,7 @@ LINEAR_ROWS = {(64, 64)}  # (cin, cout) shapes that run on mssvt_linear_rows ins
 # ... and the (cin, cout) shapes that run on mssvt_linear_rows_h (csrc/linear_rows_h.hip: split-fp16 operands, rows and weight
 # matrix normalised by powers of two inside the kernel): the Blocks' 128 <-> 256 FFN, 64 <-> 128 to_kvs, 128 x 128 pos_proj.2 --
 # the library GEMMs that were 24 % of the training step's GPU time (profiles/r04_f_train_step_kernel_stats.csv)
-LINEAR_ROWS_H = {(128, 256), (256, 128), (64, 128), (128, 64), (128, 128)} if os.environ.get("MSSVT_LINEAR_ROWS_H", "1") != "0" else set()
+LINEAR_ROWS_H = {(128, 256), (256, 128), (64, 128), (128, 64), (128, 128)}
 
 
 def _linear_rows(x, w, transpose_w, b, relu, n_out, scale=1.0, split16=False):
@@ -735,7 +734,7 @@ def _block_index_sets(block, sp, p):
     return s
 
 
-BLOCK_TAIL = os.environ.get("MSSVT_TRAIN_BLOCK_TAIL", "1") != "0"  # 0: the autograd composition (gather_sum + where + DropPath + add)
+BLOCK_TAIL = True  # False: the autograd composition (gather_sum + where + DropPath + add)
 
 
 class _BlockTail(torch.autograd.Function):

@@ -64,7 +64,7 @@ def test_frame_call_is_bit_identical_to_the_python_driven_path(points, B, monkey
 
 
 def test_frame_call_with_the_side_stream_gives_the_same_frames(monkeypatch):
-    """MSSVT_FRAME_OVERLAP: first norm1 + pillar plan on the frame object's second stream (auto for large frames)."""
+    """frame.OVERLAP: first norm1 + pillar plan on the frame object's second stream (auto for large frames)."""
     from mssvt_amd import frame
     net = _net()
     feats, vc = _scene(20000, 2, 21)

@@ -119,3 +119,41 @@ def test_height_compression_mirror_state_dict_and_cfg_keys():
     assert m.compress_layers[3].dilation == (2, 2) and m.compress_layers[3].padding == (2, 2)
     assert HeightCompression(dict(NUM_BEV_FEATURES=8, COMPRESS_LAYER_NUMS=0)).compress_layers is None
     assert m.num_bev_features == 8 and m.use_amp is False
+
+
+def _environ_names(path):
+    """The variable names a module reads or writes through `environ[...]`, `environ.get / .setdefault` or `getenv`,
+    whatever the `os` module is called there; a name that is not a string literal is reported as "<computed>"."""
+    import ast
+
+    def is_environ(node):
+        return isinstance(node, ast.Attribute) and node.attr == "environ" or isinstance(node, ast.Name) and node.id == "environ"
+
+    def name_of(node):
+        return node.value if isinstance(node, ast.Constant) and isinstance(node.value, str) else "<computed>"
+
+    with open(path) as f:
+        tree = ast.parse(f.read(), path)
+    out = set()
+    for node in ast.walk(tree):
+        if isinstance(node, ast.Subscript) and is_environ(node.value):
+            out.add(name_of(node.slice))
+        elif isinstance(node, ast.Call) and node.args:
+            fn = node.func
+            if (isinstance(fn, ast.Attribute) and fn.attr in ("get", "setdefault") and is_environ(fn.value)) or \
+                    (isinstance(fn, ast.Attribute) and fn.attr == "getenv") or (isinstance(fn, ast.Name) and fn.id == "getenv"):
+                out.add(name_of(node.args[0]))
+    return out
+
+
+def test_package_reads_no_code_path_switches_from_the_environment():
+    """Which kernels a frame runs is decided by module attributes (fused.CMP_WS, frame.ENABLED, ...), never by the
+    environment: the package touches only the library location, the checkpoint opt-in, the build's compiler, the
+    runtime's kernel-argument setting and the torchrun variables."""
+    import glob
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mssvt_amd")
+    names = set()
+    for path in sorted(glob.glob(os.path.join(root, "*.py"))):
+        names |= _environ_names(path)
+    assert names == {"MSSVT_LIB", "MSSVT_TRUST_CHECKPOINTS", "HIPCC", "MSSVT_EXTRA_HIPCC_FLAGS", "HIP_FORCE_DEV_KERNARG",
+                     "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"}

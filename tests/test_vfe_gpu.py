@@ -116,7 +116,7 @@ def test_sorted_pfn_path_equals_the_atomic_path(pts, B):
                 m.bias.normal_(0, 0.2)
     vfe = vfe.to(DEV)
     pt = torch.from_numpy(p).to(DEV)
-    assert dynamic_vfe.SORTED_PFN and dynamic_vfe.FUSED_PFN
+    assert dynamic_vfe.SORTED_PFN and vfe._fused_pfn_ok(pt)
     a = vfe(dict(points=pt, batch_size=B))
     a2 = vfe(dict(points=pt, batch_size=B))
     dynamic_vfe.SORTED_PFN = False

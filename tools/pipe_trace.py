@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """When does each frame of a pipelined run complete?  The bench loop (frames resident, inputs_ready, deferred host waits)
 with a timing event behind every frame: completion times relative to the first submission, per stream kind.
-python tools/pipe_trace.py [--steps 50] [--kinds priority,cumask]"""
+python tools/pipe_trace.py [--steps 50] [--kinds cumask,pooled]"""
 import argparse
 import os
 import sys
@@ -13,20 +13,19 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from mssvt_amd import config  # noqa: E402
-from mssvt_amd.pipeline import FramePipeline  # noqa: E402
+from mssvt_amd import config, pipeline  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=50)
-ap.add_argument("--kinds", default="priority,cumask")
+ap.add_argument("--kinds", default="cumask,pooled")
 a = ap.parse_args()
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 net = config.build_backbone_from_cfg(config.load_yaml(config.DEFAULT_CFG)).to(dev).eval()
 frames = [bench.make_inputs(160000, 1, 0, dev, frame=f) for f in range(4)]
 for kind in a.kinds.split(","):
-    os.environ["MSSVT_PIPE_STREAMS"] = kind
-    pipe = FramePipeline(net, depth=4)
+    pipeline.STREAMS = kind
+    pipe = pipeline.FramePipeline(net, depth=4)
     for rep in range(3):
         for i in range(8):
             f = frames[i % 4]

@@ -102,12 +102,13 @@ def main(out_path):
             if isinstance(m, torch.nn.BatchNorm1d):
                 m.running_mean.normal_(0, 0.3)
                 m.running_var.uniform_(0.5, 1.5)
-        assert dynamic_vfe.FUSED_PFN and dynamic_vfe.SORTED_PFN
         vfe = vfe.to(DEV)
-        out["vfe_fused"] = vfe(dict(points=torch.from_numpy(pts).to(DEV), batch_size=B))["voxel_features"].cpu().numpy()  # pfn_sorted.hip
+        pt = torch.from_numpy(pts).to(DEV)
+        assert dynamic_vfe.SORTED_PFN and vfe._fused_pfn_ok(pt)
+        out["vfe_fused"] = vfe(dict(points=pt, batch_size=B))["voxel_features"].cpu().numpy()  # pfn_sorted.hip
         dynamic_vfe.SORTED_PFN = False
         try:
-            out["vfe_atomic"] = vfe(dict(points=torch.from_numpy(pts).to(DEV), batch_size=B))["voxel_features"].cpu().numpy()  # pfn_fused.hip
+            out["vfe_atomic"] = vfe(dict(points=pt, batch_size=B))["voxel_features"].cpu().numpy()  # pfn_fused.hip
         finally:
             dynamic_vfe.SORTED_PFN = True
     np.savez(out_path, **out)

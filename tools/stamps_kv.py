@@ -5,7 +5,6 @@ import numpy as np
 import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-os.environ.setdefault("MSSVT_ATTN_KV", "1")
 import bench
 from mssvt_amd import config, fused, _lib
 torch.manual_seed(0)

@@ -13,7 +13,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import bench  # noqa: E402
-from mssvt_amd import config  # noqa: E402
+from mssvt_amd import config, pipeline  # noqa: E402
 
 
 def main():
@@ -21,7 +21,7 @@ def main():
     ap.add_argument("--batch", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--streams", type=int, default=2)
-    ap.add_argument("--kinds", default="cumask,priority,pooled", help="FramePipeline stream kinds to compare (MSSVT_PIPE_STREAMS)")
+    ap.add_argument("--kinds", default="cumask,pooled", help="FramePipeline stream kinds to compare (pipeline.STREAMS)")
     a = ap.parse_args()
     dev = torch.device("cuda", 0)
     torch.manual_seed(0)
@@ -46,7 +46,6 @@ def main():
         run(n, 20)
         t = min(run(n, a.steps) for _ in range(3))
         print("%d stream(s), one network copy each: %.3f ms per step, %.0f frames/s" % (n, t * 1e3, a.batch / t))
-    from mssvt_amd.pipeline import FramePipeline
     side = torch.cuda.Stream()
 
     def run_pipe(pipe, steps, mode):
@@ -70,9 +69,9 @@ def main():
         return (time.perf_counter() - t0) / steps
 
     for kind in a.kinds.split(","):
-        os.environ["MSSVT_PIPE_STREAMS"] = kind
+        pipeline.STREAMS = kind
         for n in ([1, a.streams] if kind == "cumask" else [a.streams]):
-            pipe = FramePipeline(net, depth=n)
+            pipe = pipeline.FramePipeline(net, depth=n)
             for mode in ("default", "side", "ready", "consume_default", "consume_side"):
                 run_pipe(pipe, 20, mode)
                 t = min(run_pipe(pipe, a.steps, mode) for _ in range(3))
