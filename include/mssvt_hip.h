@@ -696,6 +696,26 @@ int mssvt_train_unique_inverse(int nnz, int n_src, const int *idx, int *inv_scra
 long long mssvt_nms_workspace_bytes(int num_boxes);
 int mssvt_nms_bev(int num_boxes, const float *boxes_sorted, float thresh, void *workspace, int *keep,
                   int *num_keep_dev, void *stream);
+/* as mssvt_nms_bev with the axis-aligned IoU of iou_normal (heading ignored; ref nms_normal_gpu, iou3d_nms.cpp:138-188 +
+ * iou3d_nms_kernel.cu:314-372); same workspace size, same N <= 16384 */
+int mssvt_nms_normal(int num_boxes, const float *boxes_sorted, float thresh, void *workspace, int *keep,
+                     int *num_keep_dev, void *stream);
+
+/* Pairwise box measures (ref: boxes_overlap_bev_gpu / boxes_iou_bev_gpu, iou3d_nms_kernel.cu:236-265; boxes_iou3d_gpu,
+ * iou3d_nms_utils.py:48-81, fused into the launch; iou_normal :314-325).  out[i * num_b + j] =
+ *   OVERLAP_BEV  area of the intersection of the two rotated rectangles (the procedure of the NMS above)
+ *   IOU_BEV      ov / max(sa + sb - ov, 1e-8)
+ *   IOU_3D       ov3 / max(va + vb - ov3, 1e-6), ov3 = ov * max(min(za + dza/2, zb + dzb/2) - max(za - dza/2, zb - dzb/2), 0)
+ *   IOU_NORMAL   axis-aligned BEV IoU, heading ignored
+ * boxes_*: rows of >= 7 floats [x,y,z,dx,dy,dz,heading,...], stride_* floats apart (so a (N, 9) tensor with velocities
+ * needs no copy); out (num_a, num_b) f32, row-major, fully written (no need to clear it).  num_a == 0 or num_b == 0:
+ * success, nothing launched. */
+#define MSSVT_BOX_OVERLAP_BEV 0
+#define MSSVT_BOX_IOU_BEV     1
+#define MSSVT_BOX_IOU_3D      2
+#define MSSVT_BOX_IOU_NORMAL  3
+int mssvt_boxes_pairwise(int mode, int num_a, const float *boxes_a, int stride_a, int num_b, const float *boxes_b,
+                         int stride_b, float *out, void *stream);
 
 /* Weight / bias gradient of an nn.Linear over compact rows (training path; what autograd's library GEMM computes for
  * the reference's to_qs / to_kvs / projs / linear1 / linear2, ref mssvt_utils.py:80-83, mssvt_backbone.py:25-27):

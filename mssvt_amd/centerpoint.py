@@ -4,9 +4,12 @@ Mirrors the reference's ``Detector3DTemplate`` (pcdet/models/detectors/detector3
 vfe -> backbone_3d -> map_to_bev_module -> backbone_2d -> dense_head, each built from its config node and registered
 under that attribute name, so state-dict keys read ``vfe.*``, ``backbone_3d.backbone.{i}.*``, ``map_to_bev_module.*``,
 ``backbone_2d.*``, ``dense_head.*``), ``CenterPoint.forward`` / ``post_processing`` (detectors/centerpoint.py:4-50) in
-eval mode, and the checkpoint loaders ``load_params_from_file`` / ``_load_state_dict`` (:330-372: update by key where
-the shapes agree, report what stayed).  Training losses, the dataset classes, recall bookkeeping and the spconv weight
-layout adaptation (no spconv module exists here) are out of scope."""
+eval mode with the recall bookkeeping of ``generate_recall_record`` (detector3d_template.py:286-328: with ``gt_boxes`` in
+the batch, ``det(batch)`` returns ``(pred_dicts, recall_dict)`` for the eval loop to sum; the 3-D IoU comes from
+csrc/box_iou.hip, trimming and counting stay on the device, one read-back per batch), and the checkpoint loaders
+``load_params_from_file`` / ``_load_state_dict`` (:330-372: update by key where the shapes agree, report what stayed).
+The dataset classes, dataset-level AP evaluation and the spconv weight layout adaptation (no spconv module exists here)
+are out of scope."""
 import contextlib
 import os
 from types import SimpleNamespace
@@ -16,6 +19,7 @@ import torch
 from torch import nn
 
 from .base_bev_backbone import BaseBEVBackbone
+from . import iou3d_nms_utils
 from .center_head import CenterHead
 from .dynamic_vfe import DynamicVFE
 from .height_compression import HeightCompression
@@ -118,7 +122,68 @@ class CenterPoint(nn.Module):
         return self.post_processing(batch_dict)
 
     def post_processing(self, batch_dict):
-        return batch_dict["final_box_dicts"], {}  # recall bookkeeping (ref :34-50) needs ground truth: not kept
+        """(pred_dicts, recall_dict), ref centerpoint.py:36-50; recall_dict stays {} without ground truth in the batch."""
+        final_pred_dict = batch_dict["final_box_dicts"]
+        recall_dict = {}
+        if "gt_boxes" not in batch_dict:
+            return final_pred_dict, recall_dict
+        thresh_list = self.model_cfg.POST_PROCESSING.RECALL_THRESH_LIST
+        counts = [self._recall_counts(final_pred_dict[index]["pred_boxes"], index, batch_dict, thresh_list)
+                  for index in range(batch_dict["batch_size"])]
+        if counts:  # the samples' counters travel to the host together
+            recall_dict = self._recall_add(recall_dict, torch.stack(counts).sum(0).tolist(), thresh_list)
+        return final_pred_dict, recall_dict
+
+    @staticmethod
+    def generate_recall_record(box_preds, recall_dict, batch_index, data_dict=None, thresh_list=None, iou_fn=None):
+        """Adds sample `batch_index` to the recall counters (ref detector3d_template.py:286-328): 'gt' ground-truth boxes
+        seen, 'rcnn_<t>' / 'roi_<t>' those whose best 3-D IoU with a predicted box / a RoI exceeds t (strict).  Nothing
+        happens without 'gt_boxes' in `data_dict`; 'roi_*' only count when it holds 'rois'.  `iou_fn(boxes_a, boxes_b)`
+        (test hook) replaces iou3d_nms_utils.boxes_iou3d_gpu.  One read-back per call."""
+        if "gt_boxes" not in data_dict:
+            return recall_dict
+        counts = CenterPoint._recall_counts(box_preds, batch_index, data_dict, thresh_list, iou_fn)
+        return CenterPoint._recall_add(recall_dict, counts.tolist(), thresh_list)
+
+    @staticmethod
+    def _recall_add(recall_dict, counts, thresh_list):
+        """`counts` [gt, rcnn per threshold, roi per threshold] (Python ints) added to the dict, its keys made on first use."""
+        if len(recall_dict) == 0:
+            recall_dict = {"gt": 0}
+            for t in thresh_list:
+                recall_dict["roi_%s" % str(t)] = 0
+                recall_dict["rcnn_%s" % str(t)] = 0
+        nt = len(thresh_list)
+        recall_dict["gt"] += int(counts[0])
+        for k, t in enumerate(thresh_list):
+            recall_dict["rcnn_%s" % str(t)] += int(counts[1 + k])
+            recall_dict["roi_%s" % str(t)] += int(counts[1 + nt + k])
+        return recall_dict
+
+    @staticmethod
+    def _recall_counts(box_preds, batch_index, data_dict, thresh_list, iou_fn=None):
+        """int64 (1 + 2 T) [gt, rcnn_t ..., roi_t ...] of one sample, on the ground truth's device, without a host sync
+        (the reference reads one row sum per padded ground-truth row and one count per threshold back)."""
+        iou_fn = iou_fn or iou3d_nms_utils.boxes_iou3d_gpu
+        gt_boxes = data_dict["gt_boxes"][batch_index]
+        rois = data_dict["rois"][batch_index] if "rois" in data_dict else None
+        num_rows, nt = gt_boxes.shape[0], len(thresh_list)
+        if num_rows == 0:
+            return torch.zeros(1 + 2 * nt, dtype=torch.int64, device=gt_boxes.device)
+        # the reference trims trailing all-zero (padding) rows with `while k > 0 and cur_gt[k].sum() == 0`: row 0 always
+        # survives, so a sample whose ground truth is ALL padding counts ONE ground-truth box.  Reproduced: the number of
+        # rows kept is the index of the last row with a non-zero sum (0 if there is none) + 1, as a mask over the rows
+        rows = torch.arange(num_rows, device=gt_boxes.device)
+        num_gt = (rows * (gt_boxes.sum(dim=1) != 0)).max() + 1
+        kept = rows < num_gt
+
+        def recalled(boxes):
+            if boxes is None or boxes.shape[0] == 0:
+                return torch.zeros(nt, dtype=torch.int64, device=gt_boxes.device)
+            best = iou_fn(boxes[:, 0:7], gt_boxes[:, 0:7]).max(dim=0)[0]  # padded rows are zero-size boxes: IoU 0
+            return torch.stack([((best > t) & kept).sum() for t in thresh_list])
+
+        return torch.cat([num_gt.view(1), recalled(box_preds), recalled(rois)])
 
     # ---- checkpoints (ref detector3d_template.py:330-372) ----------------------------------------------------
     def _load_state_dict(self, model_state_disk, *, strict=True):

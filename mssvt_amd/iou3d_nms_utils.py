@@ -1,7 +1,15 @@
-"""Rotated BEV NMS on MI355X -- the entry point the reference's ``model_nms_utils.class_agnostic_nms`` resolves by
-name (``getattr(iou3d_nms_utils, nms_config.NMS_TYPE)``, ref: pcdet/models/model_utils/model_nms_utils.py:27-30;
-pcdet/ops/iou3d_nms/iou3d_nms_utils.py:83-98).  Same signature and return value; the suppression matrix AND the greedy
-walk run on the device (csrc/nms_bev.hip), one host sync for the number of boxes kept."""
+"""Rotated-box IoU operators and NMS on MI355X -- the GPU functions of the reference's
+``pcdet.ops.iou3d_nms.iou3d_nms_utils`` (:31-116), same names, parameter names, asserts and return values:
+
+* ``nms_gpu`` / ``nms_normal_gpu`` -- what ``model_nms_utils.class_agnostic_nms`` resolves by name
+  (``getattr(iou3d_nms_utils, nms_config.NMS_TYPE)``, ref: pcdet/models/model_utils/model_nms_utils.py:27-30).  The
+  suppression matrix AND the greedy walk run on the device (csrc/nms_bev.hip), one host sync for the number of boxes kept.
+* ``boxes_iou_bev`` / ``boxes_iou3d_gpu`` (and ``boxes_overlap_bev``, the matrix the reference's pybind module fills for
+  the 3-D IoU) -- (N, M) pair matrices from one launch of csrc/box_iou.hip; the 3-D IoU's height / volume arithmetic is
+  fused into it and rounds like the reference's torch composition.  Column slices of wider tensors (``preds[:, 0:7]``)
+  are read in place through the row stride.
+
+``boxes_bev_iou_cpu`` (the GT-database sampler's, datasets are out of scope) is not provided."""
 import ctypes
 
 import torch
@@ -17,9 +25,21 @@ def nms_gpu(boxes, scores, thresh, pre_maxsize=None, **kwargs):
     order = scores.sort(0, descending=True)[1]
     if pre_maxsize is not None:
         order = order[:pre_maxsize]
+    return _nms_ordered(boxes, order, thresh, "mssvt_nms_bev", "nms_gpu"), None
+
+
+def nms_normal_gpu(boxes, scores, thresh, **kwargs):
+    """As `nms_gpu` with the axis-aligned BEV IoU (heading ignored): (indices of the kept boxes, best first; None)."""
+    assert boxes.shape[1] == 7
+    order = scores.sort(0, descending=True)[1]
+    return _nms_ordered(boxes, order, thresh, "mssvt_nms_normal", "nms_normal_gpu"), None
+
+
+def _nms_ordered(boxes, order, thresh, entry, who):
+    """The indices of `order` (into `boxes`, descending score) that greedy NMS through `entry` keeps."""
     n = int(order.shape[0])
     if n == 0:
-        return order, None
+        return order
     if n > NMS_MAX_BOXES:
         # beyond one launch's capacity (the reference takes any N): score-ordered chunks, the boxes kept so far put in
         # front of the next chunk -- they outrank it and do not suppress each other, so greedy NMS keeps them and
@@ -28,23 +48,70 @@ def nms_gpu(boxes, scores, thresh, pre_maxsize=None, **kwargs):
         for lo in range(0, n, NMS_MAX_BOXES // 2):
             chunk = order[lo:lo + NMS_MAX_BOXES // 2]
             if kept.numel() + chunk.numel() > NMS_MAX_BOXES:
-                raise _lib.MssvtHipError("nms_gpu: more than %d boxes survive" % (NMS_MAX_BOXES // 2))
+                raise _lib.MssvtHipError("%s: more than %d boxes survive" % (who, NMS_MAX_BOXES // 2))
             cand = torch.cat([kept, chunk])
-            kept = cand[_nms_sorted(boxes[cand].float().contiguous(), thresh)]
-        return kept.contiguous(), None
+            kept = cand[_nms_sorted(boxes[cand].float().contiguous(), thresh, entry)]
+        return kept.contiguous()
     b = boxes[order].float().contiguous()
-    return order[_nms_sorted(b, thresh)].contiguous(), None
+    return order[_nms_sorted(b, thresh, entry)].contiguous()
 
 
 NMS_MAX_BOXES = 16384  # csrc/nms_bev.hip: one launch
 
+BOX_OVERLAP_BEV, BOX_IOU_BEV, BOX_IOU_3D, BOX_IOU_NORMAL = 0, 1, 2, 3  # include/mssvt_hip.h MSSVT_BOX_*
 
-def _nms_sorted(b, thresh):
-    """Indices (into `b`, best first) that greedy rotated NMS keeps among boxes already sorted by descending score."""
+
+def _rows(t):
+    """(tensor whose rows the kernel can read in place, row stride in floats): fp32 on the GPU with unit column stride
+    -- a contiguous tensor or a column slice of a wider one -- goes as it is, anything else through a contiguous copy."""
+    if not t.is_cuda:
+        raise _lib.MssvtHipError("mssvt_amd ops need tensors on the GPU (no CPU path)")
+    if t.dtype != torch.float32 or t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < 7):
+        t = t.float().contiguous()
+    return t, (int(t.stride(0)) if t.shape[0] > 1 else 7)
+
+
+def boxes_pairwise(mode, boxes_a, boxes_b, out=None):
+    """out[i, j] = measure `mode` (BOX_*) of boxes_a[i] and boxes_b[j]; (N, 7+) and (M, 7+) rows -> (N, M) float32."""
+    assert boxes_a.dim() == 2 and boxes_b.dim() == 2 and boxes_a.shape[1] >= 7 and boxes_b.shape[1] >= 7
+    a, sa = _rows(boxes_a)
+    b, sb = _rows(boxes_b)
+    n, m = int(a.shape[0]), int(b.shape[0])
+    if out is None:
+        out = torch.empty((n, m), dtype=torch.float32, device=a.device)  # fully written by the kernel
+    if not (a.device == b.device == out.device) or out.dtype != torch.float32 or tuple(out.shape) != (n, m):
+        raise _lib.MssvtHipError("boxes_pairwise: boxes_a, boxes_b and a float32 (N, M) out must share one device")
+    if n and m:
+        _lib.call("mssvt_boxes_pairwise", _i(mode), _i(n), ctypes.c_void_p(a.data_ptr()), _i(sa), _i(m),
+                  ctypes.c_void_p(b.data_ptr()), _i(sb), _lib.ptr(out), _lib.stream())
+    return out
+
+
+def boxes_overlap_bev(boxes_a, boxes_b):
+    """boxes_a (N, 7), boxes_b (M, 7) [x, y, z, dx, dy, dz, heading] -> (N, M) overlap areas in the bird's-eye view."""
+    assert boxes_a.shape[1] == boxes_b.shape[1] == 7
+    return boxes_pairwise(BOX_OVERLAP_BEV, boxes_a, boxes_b)
+
+
+def boxes_iou_bev(boxes_a, boxes_b):
+    """boxes_a (N, 7), boxes_b (M, 7) [x, y, z, dx, dy, dz, heading] -> ans_iou (N, M), rotated BEV IoU."""
+    assert boxes_a.shape[1] == boxes_b.shape[1] == 7
+    return boxes_pairwise(BOX_IOU_BEV, boxes_a, boxes_b)
+
+
+def boxes_iou3d_gpu(boxes_a, boxes_b):
+    """boxes_a (N, 7), boxes_b (M, 7) [x, y, z, dx, dy, dz, heading] -> ans_iou (N, M), 3-D IoU (BEV overlap x height
+    overlap over the union of the volumes)."""
+    assert boxes_a.shape[1] == boxes_b.shape[1] == 7
+    return boxes_pairwise(BOX_IOU_3D, boxes_a, boxes_b)
+
+
+def _nms_sorted(b, thresh, entry="mssvt_nms_bev"):
+    """Indices (into `b`, best first) that greedy NMS keeps among boxes already sorted by descending score."""
     n = int(b.shape[0])
     ws = torch.empty(int(_lib.lib().mssvt_nms_workspace_bytes(_i(n))) // 8 + 1, dtype=torch.int64, device=b.device)
     keep = torch.empty(n, dtype=torch.int32, device=b.device)
     cnt = torch.empty(1, dtype=torch.int32, device=b.device)
-    _lib.call("mssvt_nms_bev", _i(n), _lib.ptr(b), ctypes.c_float(float(thresh)), _lib.ptr(ws), _lib.ptr(keep),
+    _lib.call(entry, _i(n), _lib.ptr(b), ctypes.c_float(float(thresh)), _lib.ptr(ws), _lib.ptr(keep),
               _lib.ptr(cnt), _lib.stream())
     return keep[:int(cnt.item())].long()
