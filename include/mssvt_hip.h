@@ -273,6 +273,43 @@ int mssvt_window_plan_two(
     const int *win_counts_dev, int num_tabs, const int *host_tab_list, const int *host_tab_interp,
     const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w, void *stream);
 
+/* mssvt_window_plan_two without interpolation tables (the arguments up to win_counts_dev are the same; kmeta1 required):
+ * vox_win (N) int32, pre-filled with -1, receives for every voxel of a win1 list the window that lists it -- the input of
+ * mssvt_voxel_tables, which builds the tables with one lane per voxel instead of one wavefront per window.  For window
+ * lists that cannot overlap (as for num_tabs > 0) whose odd / even entries all lie inside the win1 list:
+ * MSSVT_E_TOOLARGE unless max_num_odd <= max_num_win1 and num_odd + max_num_even <= max_num_win1.                */
+int mssvt_window_plan_two_vox(
+    int x_max, int y_max, int z_max, int x_ws, int y_ws, int z_ws, int max_num_odd, int max_num_even,
+    int max_num_win1, int max_num_win2, int hash_size, int batch_size, int num_odd, int num_even,
+    int num_win1, int num_win2, const int *vox_query_odd, const int *vox_query_even,
+    const int *vox_query_win1, const int *vox_query_win2, int key_num_sample, const int *win_indices,
+    const int *num_wins_dev, int win_capacity, const int *xyz_to_vidx, const int *v_bs_cnt,
+    int *ind_odd, int *ind_even, int *ind_win1, int *k_ind1, int *k_ind2, unsigned char *k_mask1,
+    unsigned char *k_mask2, int *win_vstart, int *owner_win1, int *owner_odd, int *owner_even,
+    const int *indices, const float *host_voxel_size3, const float *host_range_min3,
+    const float *host_win_size3, float *qmeta_odd, float *qmeta_even, float *qmeta_win1, float *kmeta1,
+    float *kmeta2, float *wcentre, int *nq_valid, const unsigned long long *occ_columns,
+    const int *host_footprint4, const int *packed_offsets, const int *column_vbase, const int *level_status_dev,
+    const int *win_counts_dev, int *vox_win, void *stream);
+
+/* The interpolation tables of mssvt_window_plan_two(num_tabs > 0), byte for byte, from a finished plan: one lane per
+ * (voxel, table).  vox_win from mssvt_window_plan_two_vox; nq_valid (3, win_capacity) and the qmeta of every list a table
+ * names from the same plan (.w of a slot = the global feature row of its voxel); indices (N,4); the host_tab_* arrays as
+ * for mssvt_window_plan_two.  host_tab_row[t] is written for EVERY voxel ((-1,-1,-1,-1): not updated; no pre-fill
+ * needed), host_tab_w[t] for the updated ones.
+ * The same launch carries an independent second job when chunk_groups > 0: the chunk ends of mssvt_compress_ws_chunked
+ * for a grid of chunk_groups = mssvt_compress_ws_groups(win_capacity of the pillar level) workgroups -- chunk_ends
+ * (chunk_groups + 1, 2) int32 (window, row) pairs, non-decreasing, every one a window start, (0, 0) first and
+ * (*chunk_num_wins_dev, num_voxels) last, cut by cost (8 per row + 5 per window) from chunk_pair_win (N).  num_tabs = 0
+ * with chunk_groups > 0 computes the ends only.  (mssvt_frame_forward runs the same workgroups in front of those of the
+ * k_query_rows launch of its work orders instead of in a launch of their own.)                                     */
+int mssvt_voxel_tables(int num_voxels, const int *indices, const int *vox_win, const int *nq_valid, int win_capacity,
+                       const float *qmeta_odd, const float *qmeta_even, const float *qmeta_win1, int max_num_odd,
+                       int max_num_even, int max_num_win1, const float *host_voxel_size3, const float *host_range_min3,
+                       int num_tabs, const int *host_tab_list, const int *host_tab_interp, const int *host_tab_zero_row,
+                       int *const *host_tab_row, float *const *host_tab_w, int chunk_groups,
+                       const int *chunk_num_wins_dev, const int *chunk_pair_win, int *chunk_ends, void *stream);
+
 /* Occupancy columns of a voxel set (z_max <= 64): columns (B*x_max*y_max) 64-bit words, bit z of
  * word (b*x_max + x)*y_max + y set when cell (b,x,y,z) holds a voxel.  Optional input of
  * mssvt_window_plan_two (together with host_footprint4 = {min x offset, min y offset, x extent,
@@ -466,6 +503,17 @@ int mssvt_compress_ws(int C, int head_dim, float scale, int z_ws, int max_num_wi
                       const float *host_voxel_size3, const float *host_range_min3, const float *host_win_size3,
                       const float *xhat, const float *Wpos1, const float *bpos1, const float *bpos2, const float *bq,
                       const float *bkv, const float *bo, const void *packed, float *out, void *stream);
+/* The same with the chunks of the level handed in: every workgroup of mssvt_compress_ws finds its chunk (consecutive windows
+ * holding 1 / grid of the cost) by a search of its own; chunk_ends (chunk_groups + 1, 2) from mssvt_voxel_tables replaces the
+ * search (chunk_groups must equal mssvt_compress_ws_groups(win_capacity), the number of workgroups; NULL: search).  The
+ * output does not depend on where the chunks are cut.                                                            */
+int mssvt_compress_ws_groups(int win_capacity);
+int mssvt_compress_ws_chunked(int C, int head_dim, float scale, int z_ws, int max_num_win1, int num_voxels,
+                              const int *num_wins_dev, int win_capacity, const int *indices, const int *win_cnt,
+                              const int *pair_win, const float *host_voxel_size3, const float *host_range_min3,
+                              const float *host_win_size3, const float *xhat, const float *Wpos1, const float *bpos1,
+                              const float *bpos2, const float *bq, const float *bkv, const float *bo, const void *packed,
+                              float *out, const int *chunk_ends, int chunk_groups, void *stream);
 
 /* Backward of mssvt_layer_norm (training path; autograd's LayerNorm backward in the reference): dx (N,C), dweight (C),
  * dbias (C) from x, dy; mean / rstd are recomputed.  The column sums are per-workgroup partial rows in `workspace`

@@ -11,7 +11,7 @@
 // One workgroup of C / 16 waves per CU; wave w keeps, as split-fp16 MFMA A-fragments (see ffn.hip, k_ffn_ws) in REGISTERS for
 // the whole launch, rows [16 w, 16 w + 16) of pos_proj.2, Wk and Wv -- i.e. everything of HEAD w -- and reads its rows of
 // Wq and Wo from LDS (used once per 16 windows).  The workgroup owns a CHUNK: consecutive windows = consecutive rows holding
-// 1 / gridDim of the cost (rows and windows weighed 8 : 5), found by 4096 probes of pair_win.  The chunk is walked as a
+// 1 / gridDim of the cost (rows and windows weighed 8 : 5), found by 4096 probes of pair_win -- or handed in (CwArgs::ends).  The chunk is walked as a
 // STREAM of 16-row pieces, whatever the windows; windows are taken in GROUPS of 16 for the two window-side products:
 //   per piece of 16 rows:
 //   S1   h = relu(pos_proj.0 [rel ; centre] + b): each wave its 16 channels, split, published as B fragments  [barrier]
@@ -56,6 +56,7 @@ struct CwArgs {
     const float *xhat;
     const float *Wp1, *bp1, *bp2, *bq, *bkv, *bo;
     float *out;
+    const int2 *ends;  // optional: the gridDim + 1 chunk ends (window, row) of mssvt_voxel_tables -- no search in the prologue
 };
 
 __device__ __forceinline__ int lane_pick4i(int g, int x, int y, int z, int w) {
@@ -182,7 +183,13 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
     // numbered in row order).  4096 probes -> the first probe at or above c total / gridDim -> the next window START at or
     // after it.  Every workgroup evaluates both of its ends with the same function: the chunks tile the level.
     int Wa, Wb, Ra, Rb;
-    {
+    if (a.ends) {  // (workgroup-uniform) computed once for the whole grid by a launch before this one
+        const int2 e0 = a.ends[blockIdx.x], e1 = a.ends[blockIdx.x + 1];
+#pragma unroll
+        for (int u = 0; u < WCP; ++u) wq_l[threadIdx.x + u * T] = wcp[u];
+        Wa = __builtin_amdgcn_readfirstlane(e0.x); Ra = __builtin_amdgcn_readfirstlane(e0.y);
+        Wb = __builtin_amdgcn_readfirstlane(e1.x); Rb = __builtin_amdgcn_readfirstlane(e1.y);
+    } else {
         constexpr int NPB = 8, NPROBE = NPB * T;
         int *ps = reinterpret_cast<int *>(hfrag);  // [probes] (16 KB: hfrag | kfrag), results behind the max tile's start
         static_assert(NPROBE * 4 <= 2 * FR * 16, "probes fit the two fragment sets");
@@ -654,12 +661,22 @@ extern "C" int mssvt_compress_ws_pack(int C, const float *Wpos2, const float *Wq
 // _compress_ws_ok): a level set up as SORTED (mssvt_level_setup_sorted: windows numbered in row order), pillar windows
 // x_ws = y_ws = 1 with max_num_win1 >= z_ws and <= 32 (no list is truncated: a window is one run of rows), one head group,
 // head_dim 16, C = 128, operands inside the fp16 range (fused._compress_f16_ok).  MSSVT_E_TOOLARGE for other shapes.
-extern "C" int mssvt_compress_ws(int C, int head_dim, float scale, int z_ws, int max_num_win1, int num_voxels,
+// workgroups of k_cmp_ws for a window capacity = chunks of the level (the G of mssvt_voxel_tables' chunk ends)
+extern "C" int mssvt_compress_ws_groups(int win_capacity) {
+    if (win_capacity <= 0) return 0;
+    int dev = 0, cus = 256;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
+    if (cus < 1) cus = 256;
+    const int tiles = (win_capacity + 15) / 16;
+    return tiles < cus ? tiles : cus;
+}
+
+extern "C" int mssvt_compress_ws_chunked(int C, int head_dim, float scale, int z_ws, int max_num_win1, int num_voxels,
                                  const int *num_wins_dev, int win_capacity, const int *indices, const int *win_cnt,
                                  const int *pair_win, const float *host_voxel_size3,
                                  const float *host_range_min3, const float *host_win_size3, const float *xhat, const float *Wpos1,
                                  const float *bpos1, const float *bpos2, const float *bq, const float *bkv, const float *bo,
-                                 const void *packed, float *out, void *stream) {
+                                 const void *packed, float *out, const int *chunk_ends, int chunk_groups, void *stream) {
     if (!num_wins_dev || !indices || !win_cnt || !pair_win || !host_voxel_size3 ||
         !host_range_min3 || !host_win_size3 || !xhat || !Wpos1 || !bpos1 || !bpos2 || !bq || !bkv || !bo || !packed || !out ||
         max_num_win1 <= 0 || num_voxels < 0 || win_capacity <= 0 || z_ws <= 0)
@@ -679,10 +696,21 @@ extern "C" int mssvt_compress_ws(int C, int head_dim, float scale, int z_ws, int
     static_assert((size_t)(2 * (128 / 16) * ((128 / 32) * 2 * 64) + 3 * ((128 / 32) * 2 * 64)) * 16 + 16 * 128 * 4 <= 160 * 1024, "LDS budget");
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_cmp_ws<CC>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) cus = 256;
-    const int tiles = (win_capacity + 15) / 16;
-    const int grid = tiles < cus ? tiles : cus;
+    const int grid = mssvt_compress_ws_groups(win_capacity);
+    // chunk ends are those of exactly this grid (mssvt_voxel_tables(chunk_groups = mssvt_compress_ws_groups(win_capacity)))
+    if (chunk_ends && chunk_groups != grid) return MSSVT_E_BADARG;
+    a.ends = reinterpret_cast<const int2 *>(chunk_ends);
     k_cmp_ws<CC><<<grid, NW * MSSVT_WAVE, lds, (hipStream_t)stream>>>(a, reinterpret_cast<const h16x8 *>(packed));
     return mssvt_launch_status();
+}
+
+extern "C" int mssvt_compress_ws(int C, int head_dim, float scale, int z_ws, int max_num_win1, int num_voxels,
+                                 const int *num_wins_dev, int win_capacity, const int *indices, const int *win_cnt,
+                                 const int *pair_win, const float *host_voxel_size3,
+                                 const float *host_range_min3, const float *host_win_size3, const float *xhat, const float *Wpos1,
+                                 const float *bpos1, const float *bpos2, const float *bq, const float *bkv, const float *bo,
+                                 const void *packed, float *out, void *stream) {
+    return mssvt_compress_ws_chunked(C, head_dim, scale, z_ws, max_num_win1, num_voxels, num_wins_dev, win_capacity, indices, win_cnt,
+                                     pair_win, host_voxel_size3, host_range_min3, host_win_size3, xhat, Wpos1, bpos1, bpos2, bq, bkv,
+                                     bo, packed, out, nullptr, 0, stream);
 }

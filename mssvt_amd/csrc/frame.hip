@@ -3,25 +3,30 @@
 // The reference's MixedScaleSparseTransformer.forward (ref: pcdet/models/backbones_3d/mssvt_backbone.py:450-472) drives its
 // blocks from Python: ~100 launches and >= 5B + 2 host syncs per Block.  mssvt_amd/fused.py cut that to ~34 launches and no
 // sync, but the ~65 allocations, ~15 ctypes calls and the bookkeeping around them still cost ~630 us of interpreter time
-// per frame -- as much as the kernels.  Here the same sequence of the SAME entry points (same arguments, same order:
-// results are bit-identical to the Python-driven fused path) is issued from C++ out of one caller-owned workspace:
+// per frame -- as much as the kernels.  Here the same sequence of entry points (results are bit-identical to the Python-driven
+// fused path, which still builds its interpolation tables inside the plan kernel and lets k_cmp_ws search its chunks) is
+// issued from C++ out of one caller-owned workspace:
 //
 //     fill (-1 arena, zero region, the output table) + the first norm1 in the same launch    k_frame_fill_ln
 //     level set-up of the (b,x,y,z)-sorted input list + early device-to-host copy            mssvt_level_setup_sorted_pillars
-//     window plan of the two-scale Blocks (+ interpolation tables), work orders              mssvt_window_plan_two, mssvt_plan_order_multi
+//     window plan of the two-scale Blocks                                                    mssvt_window_plan_two_vox
+//     work orders; in the launch of their query rows, the interpolation tables per voxel
+//     and the CompressBlock's chunk ends                                                     mssvt_plan_order_multi_vt (voxel_tables.hip.h)
 //     per Block: window attention, FFN tail (emits the next block's norm1)                   mssvt_block_attention*, mssvt_ffn_fused_interp
-//     CompressBlock: attention (its pillar lists come out of the level set-up), FFN tail      mssvt_compress_fused, mssvt_ffn_fused
+//     CompressBlock: attention (its pillar lists come out of the level set-up), FFN tail      mssvt_compress_ws_chunked / _fused, mssvt_ffn_fused
 //
 // A frame object (mssvt_frame_create) only holds the description of the network: window configuration, parameter
 // pointers (device memory owned by the caller), one pinned 4-KiB host buffer and one event for the frame's single
 // device-to-host hand-over (status words + the data-dependent output row count).  It launches on the caller's stream,
 // allocates nothing per frame and keeps no device state between frames.  Shapes it does not cover return
 // MSSVT_E_TOOLARGE from the add_* calls: the caller keeps its own path for those (mssvt_amd/fused.py).
+#include <algorithm>
 #include <new>
 #include <vector>
 
 #include "common.hip.h"
 #include "../../include/mssvt_hip.h"
+#include "voxel_tables.hip.h"
 
 namespace {
 
@@ -79,6 +84,7 @@ struct Frame {
     int overlap = 0;
     hipStream_t side = nullptr;
     hipEvent_t fork = nullptr, join = nullptr;
+    int cmp_cus = 0;  // compute units k_cmp_ws spreads over (mssvt_compress_ws_groups of an unbounded level), asked once
 };
 
 constexpr int FR_HOST_WORDS = 1024;
@@ -155,6 +161,12 @@ struct Layout {
     int *neg0;
     size_t neg_ints;
     int *tab_rows, *pair_win;
+    // the interpolation tables come from mssvt_voxel_tables (one lane per voxel and table) instead of the plan kernel: vox_win
+    // (-1 arena) = per voxel the window that lists it; tab_rows is then written for every voxel and leaves the arena
+    bool vox_tables;
+    int *vox_win;
+    int *c_ends;   // chunk ends of mssvt_compress_ws_chunked: (c_groups + 1) x (window, row)
+    int c_groups;  // 0: k_cmp_ws searches its chunk itself
     // zero region
     int *zero0;
     size_t zero_ints;
@@ -204,7 +216,10 @@ void make_layout(const Frame &f, int n, char *base, Layout &L) {
     }
     // ---- -1 arena
     L.neg0 = b.take<int>(0);
-    L.tab_rows = b.take<int>(ints_al((size_t)L.n_tabs * N * 4));
+    // (needs odd / even entries inside the win1 list: mssvt_window_plan_two_vox)
+    L.vox_tables = p.n_o <= p.n1 && p.num_o + p.n_e <= p.n1;
+    L.tab_rows = L.vox_tables ? nullptr : b.take<int>(ints_al((size_t)L.n_tabs * N * 4));
+    L.vox_win = L.vox_tables ? b.take<int>(ints_al(N)) : nullptr;
     L.pair_win = b.take<int>(ints_al(cap));
     // (the K4 lists themselves only for the three-launch form; the level set-up writes the listed slots only)
     L.c_k_ind = f.has_cmp && !f.cmp.ws_packed ? b.take<int>(ints_al(cap * (size_t)f.cmp.ns)) : nullptr;
@@ -247,6 +262,10 @@ void make_layout(const Frame &f, int n, char *base, Layout &L) {
     L.wcentre = b.take<float>(cap * 4);
     L.nq_valid = b.take<int>(3 * cap);
     L.tab_w = b.take<float>((size_t)L.n_tabs * N * 4);
+    if (L.vox_tables) L.tab_rows = b.take<int>((size_t)L.n_tabs * N * 4);
+    // = mssvt_compress_ws_groups(cap) without asking the device on every call (mssvt_compress_ws_chunked refuses another count)
+    L.c_groups = f.has_cmp && f.cmp.ws_packed ? (int)std::min<long long>(((long long)cap + 15) / 16, f.cmp_cus) : 0;
+    L.c_ends = b.take<int>(2 * ((size_t)L.c_groups + 1));
     for (int i = 0; i < L.n_pat; ++i) {
         L.perm[i] = b.take<int>(cap);
         L.n_act[i] = b.take<int>(1);
@@ -449,6 +468,7 @@ extern "C" int mssvt_frame_add_compress(
     // range) and no list can be truncated -- a window is then one run of rows of the sorted level
     c.ws_packed = compress_ws_packed && f->C == 128 && head_dim == 16 && host_win_size3[2] <= max_num_win1 && max_num_win1 <= 32
                       ? compress_ws_packed : nullptr;
+    f->cmp_cus = c.ws_packed ? mssvt_compress_ws_groups(0x7fffffff - 15) : 0;
     f->has_cmp = true;
     return MSSVT_OK;
 }
@@ -558,16 +578,23 @@ extern "C" int mssvt_frame_forward(void *frame, int num_voxels, const float *fea
     // ---- window plan of the Blocks, with the interpolation tables of every (pattern, interpolation) variant
     const float mn3[3] = {f->range[0], f->range[1], f->range[2]};
     const float wsm[3] = {f->vs[0] * p.ws[0], f->vs[1] * p.ws[1], f->vs[2] * p.ws[2]};
-    {
-        int tab_list[4], tab_zero[4];
-        int *tab_row[4];
-        float *tab_w[4];
-        for (int t = 0; t < L.n_tabs; ++t) {
-            tab_list[t] = q_list(L.tab_pat[t]);
-            tab_zero[t] = L.attn_zero_row[pattern_slot(L, L.tab_pat[t])];
-            tab_row[t] = L.tab_rows + (size_t)t * n * 4;
-            tab_w[t] = L.tab_w + (size_t)t * n * 4;
-        }
+    int tab_list[4], tab_zero[4];
+    int *tab_row[4];
+    float *tab_w[4];
+    for (int t = 0; t < L.n_tabs; ++t) {
+        tab_list[t] = q_list(L.tab_pat[t]);
+        tab_zero[t] = L.attn_zero_row[pattern_slot(L, L.tab_pat[t])];
+        tab_row[t] = L.tab_rows + (size_t)t * n * 4;
+        tab_w[t] = L.tab_w + (size_t)t * n * 4;
+    }
+    if (L.vox_tables) {
+        FR_TRY_FORKED(mssvt_window_plan_two_vox(
+            X, Y, Z, p.ws[0], p.ws[1], p.ws[2], p.n_o, p.n_e, p.n1, p.n2, H, B, p.num_o, p.num_e, p.num_1, p.num_2, p.t_o, p.t_e,
+            p.t_1, p.t_2, p.K, L.win_blk, L.hdr[0] + 1, cap, nullptr, L.cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+            nullptr, L.win_vstart, nullptr, nullptr, nullptr, indices, f->vs, mn3, wsm, L.qmeta[0], L.qmeta[1], L.qmeta[2],
+            L.kmeta[0], L.kmeta[1], L.wcentre, L.nq_valid, L.occ, p.fp4, p.packed_offsets, L.vbase, L.status, L.vcount_blk,
+            L.vox_win, stream));
+    } else {
         FR_TRY_FORKED(mssvt_window_plan_two(
             X, Y, Z, p.ws[0], p.ws[1], p.ws[2], p.n_o, p.n_e, p.n1, p.n2, H, B, p.num_o, p.num_e, p.num_1, p.num_2, p.t_o, p.t_e,
             p.t_1, p.t_2, p.K, L.win_blk, L.hdr[0] + 1, cap, nullptr, L.cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -588,8 +615,16 @@ extern "C" int mssvt_frame_forward(void *frame, int num_voxels, const float *fea
         }
         // (counting the order histograms inside the plan kernel with atomics was measured: the plan kernel +16.7 us for the
         // 4.9 us launch it saves)
-        FR_TRY_FORKED(mssvt_plan_order_multi(L.n_pat, L.hdr[0] + 1, nqv, nq, qm, cap, (int)L.row_cap, L.perm, L.n_act, L.q_off, L.row_meta,
-                                      L.row_src, L.n_rows, stream));
+        // ---- interpolation tables, one lane per (voxel, table), and the CompressBlock's chunk ends: workgroups of the k_query_rows
+        // launch (as a launch of its own, mssvt_voxel_tables, they cost the frame a second launch floor: DESIGN 5.5)
+        VtArgs vt;
+        const bool ride = L.vox_tables || L.c_groups > 0;
+        if (ride)
+            FR_TRY_FORKED(vt_make_args(vt, n, indices, L.vox_win, L.nq_valid, cap, L.qmeta[0], L.qmeta[1], L.qmeta[2], p.n_o, p.n_e, p.n1,
+                                       f->vs, mn3, L.vox_tables ? L.n_tabs : 0, tab_list, L.tab_interp, tab_zero, tab_row, tab_w,
+                                       L.c_groups, L.hdr[1] + 1, L.pair_win, L.c_ends));
+        FR_TRY_FORKED(mssvt_plan_order_multi_vt(L.n_pat, L.hdr[0] + 1, nqv, nq, qm, cap, (int)L.row_cap, L.perm, L.n_act, L.q_off,
+                                                L.row_meta, L.row_src, L.n_rows, ride ? &vt : nullptr, stream));
     }
     if (f->overlap) {
         const hipError_t e = hipStreamWaitEvent(stream, f->join, 0);
@@ -635,9 +670,9 @@ extern "C" int mssvt_frame_forward(void *frame, int num_voxels, const float *fea
     // ---- CompressBlock: attention (one launch on a sorted pillar level, else three), FFN tail over the live windows
     const float cwsm[3] = {f->vs[0] * c.ws[0], f->vs[1] * c.ws[1], f->vs[2] * c.ws[2]};
     if (c.ws_packed) {
-        FR_TRY(mssvt_compress_ws(C, c.head_dim, c.scale, c.ws[2], c.ns, n, L.hdr[1] + 1, cap, indices, L.c_win_cnt, L.pair_win,
-                                 f->vs, mn3, cwsm, xhat, c.Wp1, c.bp1, c.bp2, c.bq, c.bkv, c.bo, c.ws_packed,
-                                 L.c_new, stream));
+        FR_TRY(mssvt_compress_ws_chunked(C, c.head_dim, c.scale, c.ws[2], c.ns, n, L.hdr[1] + 1, cap, indices, L.c_win_cnt, L.pair_win,
+                                         f->vs, mn3, cwsm, xhat, c.Wp1, c.bp1, c.bp2, c.bq, c.bkv, c.bo, c.ws_packed, L.c_new,
+                                         L.c_groups > 0 ? L.c_ends : nullptr, L.c_groups, stream));
     } else {
         FR_TRY(mssvt_compress_fused(C, c.head_dim, c.scale, c.ns, n, L.hdr[1] + 1, cap, out_indices, indices, L.c_k_ind, L.c_win_vstart,
                                     L.c_win_cnt, L.pair_win, f->vs, mn3, cwsm, xhat, c.Wp1, c.bp1, c.Wp2, c.bp2, c.Wq, c.bq, c.Wkv,

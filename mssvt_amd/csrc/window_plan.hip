@@ -20,6 +20,7 @@
 // The number of windows is read from DEVICE memory (no host round trip); the grid
 // is sized for the capacity and surplus waves exit.
 #include "common.hip.h"
+#include "voxel_tables.hip.h"
 #define PLAN_MAX_WPB 4
 #ifndef PLAN_WAVES_PER_SIMD
 #define PLAN_WAVES_PER_SIMD 5  // register budget of the common instantiation (96 VGPRs; 8, 6 and 4 waves measured the same)
@@ -66,6 +67,9 @@ struct PlanArgs {
     // (query list, interpolation) variants -- built here, where the window's lists sit in LDS, when the lists of
     // different windows cannot overlap (every voxel then has one owner: this window)
     int n_tabs, tab_q;  // tab_q: candidate slots per wave (largest query list + 3)
+    // optional (mssvt_window_plan_two_vox): per voxel of a win1 list the window that lists it, for the per-voxel table
+    // kernel (voxel_tables.hip) -- then no table is built here
+    int *vox_win;
     struct PlanTab {
         int list, maxn, interp, zero_row;  // list: 0 odd, 1 even, 2 win1 (the queries); zero_row: attention row of zeros
         int4 *tab_row;
@@ -306,7 +310,10 @@ __device__ __forceinline__ void plan_emit_list(int w, int lane, int maxn, int nv
 // holds no hash probe at all -- besides the probes themselves this matters for the STORES: a load in a probe loop
 // whose last result may stay unconsumed makes the compiler wait vmcnt(0) wherever its register is reused, i.e. for
 // every store issued since (vmcnt retires in order: 5 full write round trips per window, 40 of 65 us of this kernel).
-template <int FPS_TPL, bool RANKED>
+//
+// TABS = the interpolation-table phase is compiled in (false: the instantiation of the whole-frame call, whose tables come
+// from voxel_tables.hip).
+template <int FPS_TPL, bool RANKED, bool TABS = true>
 __global__ void __launch_bounds__(PLAN_MAX_WPB *MSSVT_WAVE, FPS_TPL <= 4 ? PLAN_WAVES_PER_SIMD : 1) k_window_plan(PlanArgs a) {
     extern __shared__ int lds[];
     const int wv = threadIdx.x / MSSVT_WAVE, lane = lane_id();
@@ -494,7 +501,9 @@ __global__ void __launch_bounds__(PLAN_MAX_WPB *MSSVT_WAVE, FPS_TPL <= 4 ? PLAN_
     // ---- interpolation tables (see PlanArgs::tabs) ----------------------------------------------------------
     // Lanes are dealt to (table, win1 slot) pairs: with n1 <= 32 entries two tables go through the 3-NN search side by
     // side (lanes 0-31 / 32-63), with n1 <= 16 four; the candidates of table t sit in cand + 4 t tab_q.
-    if (a.n_tabs > 0) {
+    if (a.vox_win)  // (lists of different windows do not overlap: one store per listed voxel)
+        for (int sl = lane; sl < n1; sl += MSSVT_WAVE) a.vox_win[vstart + hsv[sl]] = w;
+    if (TABS && a.n_tabs > 0) {
         const int per = n1 <= 16 ? 16 : n1 <= 32 ? 32 : 64, side = MSSVT_WAVE / per;  // lanes per table, tables side by side
         for (int t0 = 0; t0 < a.n_tabs; t0 += side) {
             // candidates of tables t0 .. t0 + side - 1: known points = ALL query slots; empty slots sit at the world origin
@@ -658,7 +667,7 @@ static inline int plan_opt_n_threads(int work_size) {  // ref cuda_utils.h:10-14
     return v;
 }
 
-extern "C" int mssvt_window_plan_two(
+static int plan_two_launch(
     int x_max, int y_max, int z_max, int x_ws, int y_ws, int z_ws, int max_num_odd, int max_num_even,
     int max_num_win1, int max_num_win2, int hash_size, int batch_size, int num_odd, int num_even,
     int num_win1, int num_win2, const int *vox_query_odd, const int *vox_query_even,
@@ -671,7 +680,7 @@ extern "C" int mssvt_window_plan_two(
     float *kmeta2, float *wcentre, int *nq_valid, const unsigned long long *occ_columns,
     const int *host_footprint4, const int *packed_offsets, const int *column_vbase, const int *level_status_dev,
     const int *win_counts_dev, int num_tabs, const int *host_tab_list, const int *host_tab_interp,
-    const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w, void *stream) {
+    const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w, int *vox_win, void *stream) {
     // (ind_* / k_ind* / k_mask* / owner_*: each optional when the resolved metadata is asked for -- the fused consumers read
     // kmeta / qmeta / the tables; without metadata they are the call's only outputs)
     const bool lists_wanted = ind_odd && ind_even && ind_win1 && k_ind1 && k_ind2 && k_mask1 && k_mask2 && owner_win1 && owner_odd && owner_even;
@@ -733,6 +742,8 @@ extern "C" int mssvt_window_plan_two(
     a.win_counts = win_counts_dev;
     a.n_tabs = 0;
     a.tab_q = 0;
+    a.vox_win = vox_win;
+    if (vox_win && (num_tabs != 0 || !kmeta1)) return MSSVT_E_BADARG;
     if (num_tabs < 0 || num_tabs > 4) return MSSVT_E_TOOLARGE;
     if (num_tabs > 0) {
         if (!kmeta1 || !host_tab_list || !host_tab_interp || !host_tab_zero_row || !host_tab_row || !host_tab_w) return MSSVT_E_BADARG;
@@ -788,8 +799,16 @@ extern "C" int mssvt_window_plan_two(
     const int tpl = bsmax > 512 ? 16 : bsmax > 256 ? 8 : 4;
     const bool ranked = a.col_vbase != nullptr;
     typedef void (*plan_kernel_t)(PlanArgs);
-    const plan_kernel_t kernel = ranked ? (tpl == 16 ? k_window_plan<16, true> : tpl == 8 ? k_window_plan<8, true> : k_window_plan<4, true>)
-                                        : (tpl == 16 ? k_window_plan<16, false> : tpl == 8 ? k_window_plan<8, false> : k_window_plan<4, false>);
+    // The instantiation without the table phase (TABS = false) exists for the one shape the whole-frame call plans at -- ranked
+    // columns, 4-slot sampler -- and only mssvt_window_plan_two_vox (vox_win set) selects it.  Every other caller, with
+    // num_tabs == 0 too, runs the TABS = true kernel as before: with n_tabs == 0 its table phase is an empty loop.
+    plan_kernel_t kernel;
+    if (vox_win && ranked && tpl == 4)
+        kernel = k_window_plan<4, true, false>;
+    else if (ranked)
+        kernel = tpl == 16 ? k_window_plan<16, true> : tpl == 8 ? k_window_plan<8, true> : k_window_plan<4, true>;
+    else
+        kernel = tpl == 16 ? k_window_plan<16, false> : tpl == 8 ? k_window_plan<8, false> : k_window_plan<4, false>;
     if (lds_bytes > 64 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return (int)e;
@@ -798,6 +817,43 @@ extern "C" int mssvt_window_plan_two(
     hipStream_t st = (hipStream_t)stream;
     kernel<<<grid, block, lds_bytes, st>>>(a);
     return mssvt_launch_status();
+}
+
+#define PLAN_TWO_PARAMS                                                                                               \
+    int x_max, int y_max, int z_max, int x_ws, int y_ws, int z_ws, int max_num_odd, int max_num_even, int max_num_win1, \
+        int max_num_win2, int hash_size, int batch_size, int num_odd, int num_even, int num_win1, int num_win2,       \
+        const int *vox_query_odd, const int *vox_query_even, const int *vox_query_win1, const int *vox_query_win2,   \
+        int key_num_sample, const int *win_indices, const int *num_wins_dev, int win_capacity, const int *xyz_to_vidx, \
+        const int *v_bs_cnt, int *ind_odd, int *ind_even, int *ind_win1, int *k_ind1, int *k_ind2,                   \
+        unsigned char *k_mask1, unsigned char *k_mask2, int *win_vstart, int *owner_win1, int *owner_odd,            \
+        int *owner_even, const int *indices, const float *host_voxel_size3, const float *host_range_min3,            \
+        const float *host_win_size3, float *qmeta_odd, float *qmeta_even, float *qmeta_win1, float *kmeta1,          \
+        float *kmeta2, float *wcentre, int *nq_valid, const unsigned long long *occ_columns,                         \
+        const int *host_footprint4, const int *packed_offsets, const int *column_vbase, const int *level_status_dev, \
+        const int *win_counts_dev
+#define PLAN_TWO_ARGS                                                                                                  \
+    x_max, y_max, z_max, x_ws, y_ws, z_ws, max_num_odd, max_num_even, max_num_win1, max_num_win2, hash_size, batch_size, \
+        num_odd, num_even, num_win1, num_win2, vox_query_odd, vox_query_even, vox_query_win1, vox_query_win2,         \
+        key_num_sample, win_indices, num_wins_dev, win_capacity, xyz_to_vidx, v_bs_cnt, ind_odd, ind_even, ind_win1,  \
+        k_ind1, k_ind2, k_mask1, k_mask2, win_vstart, owner_win1, owner_odd, owner_even, indices, host_voxel_size3,   \
+        host_range_min3, host_win_size3, qmeta_odd, qmeta_even, qmeta_win1, kmeta1, kmeta2, wcentre, nq_valid,        \
+        occ_columns, host_footprint4, packed_offsets, column_vbase, level_status_dev, win_counts_dev
+
+extern "C" int mssvt_window_plan_two(PLAN_TWO_PARAMS, int num_tabs, const int *host_tab_list, const int *host_tab_interp,
+                                     const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w,
+                                     void *stream) {
+    return plan_two_launch(PLAN_TWO_ARGS, num_tabs, host_tab_list, host_tab_interp, host_tab_zero_row, host_tab_row, host_tab_w,
+                           nullptr, stream);
+}
+
+// The same plan without tables: vox_win (N ints, pre-filled with -1) receives, for every voxel of a win1 list, the window
+// that lists it -- the input of mssvt_voxel_tables.  For window lists that cannot overlap (as the tables of
+// mssvt_window_plan_two) whose odd / even entries all lie inside the win1 list: max_num_odd <= max_num_win1 and
+// num_odd + max_num_even <= max_num_win1 (MSSVT_E_TOOLARGE otherwise).
+extern "C" int mssvt_window_plan_two_vox(PLAN_TWO_PARAMS, int *vox_win, void *stream) {
+    if (!vox_win || !kmeta1) return MSSVT_E_BADARG;
+    if (max_num_odd > max_num_win1 || num_odd + max_num_even > max_num_win1) return MSSVT_E_TOOLARGE;
+    return plan_two_launch(PLAN_TWO_ARGS, 0, nullptr, nullptr, nullptr, nullptr, nullptr, vox_win, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1020,16 +1076,16 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
 
 // compact query rows: row q_off[w] + p = the p-th valid slot of window w's query list:
 // rmeta = the slot's (rel.xyz, bits(feature row)), rsrc = (window, attn row w * nq + slot)
-__global__ void __launch_bounds__(256) k_query_rows(const int *num_wins, int row_capacity, PlanOrderPack pack) {
-    const PlanOrderSet &ps = pack.s[blockIdx.y];
+__device__ __forceinline__ void query_rows_block(const PlanOrderSet &ps, const int nw, const int row_capacity, const int bx,
+                                                 const int gx) {
     const int nq = ps.nq;
     const float4 *qmeta = ps.qmeta;
     const int *q_off = ps.q_off;
     float4 *rmeta = ps.rmeta;
     int2 *rsrc = ps.rsrc;
-    const int nw = *num_wins, lane = lane_id();
-    const int wstep = gridDim.x * (blockDim.x / MSSVT_WAVE);
-    for (int w = blockIdx.x * (blockDim.x / MSSVT_WAVE) + threadIdx.x / MSSVT_WAVE; w < nw; w += wstep) {
+    const int lane = lane_id();
+    const int wstep = gx * (blockDim.x / MSSVT_WAVE);
+    for (int w = bx * (blockDim.x / MSSVT_WAVE) + threadIdx.x / MSSVT_WAVE; w < nw; w += wstep) {
         int run = q_off[w];
         for (int q0 = 0; q0 < nq; q0 += MSSVT_WAVE) {
             const int qi = q0 + lane;
@@ -1050,11 +1106,29 @@ __global__ void __launch_bounds__(256) k_query_rows(const int *num_wins, int row
     }
 }
 
-extern "C" int mssvt_plan_order_multi(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid,
-                                      const int *host_nq, const float *const *host_qmeta, int win_capacity,
-                                      int row_capacity, int *const *host_perm, int *const *host_num_active,
-                                      int *const *host_q_off, float *const *host_qrow_meta,
-                                      int *const *host_qrow_src, int *const *host_num_rows, void *stream) {
+__global__ void __launch_bounds__(256) k_query_rows(const int *num_wins, int row_capacity, PlanOrderPack pack) {
+    query_rows_block(pack.s[blockIdx.y], *num_wins, row_capacity, blockIdx.x, gridDim.x);
+}
+
+// k_query_rows with the workgroups of the voxel-table launch (voxel_tables.hip.h) in FRONT of its own: both jobs only read what
+// the plan kernel and k_plan_order left, neither reads the other's output, and a second light launch costs its launch floor
+// again.  The table workgroups go first because a lane of theirs is a chain of four dependent loads; the query-row workgroups
+// (x = qr_grid per list, lists along the rest of the 1-D grid) fill in behind them.
+__global__ void __launch_bounds__(256) k_query_rows_vt(const int *num_wins, int row_capacity, PlanOrderPack pack, int qr_grid,
+                                                       int vt_grid, VtArgs vt) {
+    const int b = blockIdx.x;
+    if (b < vt_grid) {
+        vt_block(vt, b);
+        return;
+    }
+    const int set = (b - vt_grid) / qr_grid;  // workgroup-uniform
+    query_rows_block(pack.s[set], *num_wins, row_capacity, (b - vt_grid) - set * qr_grid, qr_grid);
+}
+
+int mssvt_plan_order_multi_vt(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid, const int *host_nq,
+                              const float *const *host_qmeta, int win_capacity, int row_capacity, int *const *host_perm,
+                              int *const *host_num_active, int *const *host_q_off, float *const *host_qrow_meta,
+                              int *const *host_qrow_src, int *const *host_num_rows, const VtArgs *vt, void *stream) {
     if (num_sets <= 0 || num_sets > PO_MAX_SETS) return num_sets <= 0 ? MSSVT_E_BADARG : MSSVT_E_TOOLARGE;
     if (!num_wins_dev || !host_nq_valid || !host_nq || !host_qmeta || !host_perm || !host_num_active || !host_q_off ||
         !host_qrow_meta || !host_qrow_src || !host_num_rows || win_capacity <= 0 || row_capacity <= 0)
@@ -1087,8 +1161,21 @@ extern "C" int mssvt_plan_order_multi(int num_sets, const int *num_wins_dev, con
     }
     int grid = (win_capacity + 3) / 4;
     if (grid > 4096) grid = 4096;
-    k_query_rows<<<dim3(grid, num_sets), 256, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
+    const int vt_grid = vt ? vt_blocks(*vt) : 0;
+    if (vt_grid > 0)
+        k_query_rows_vt<<<vt_grid + grid * num_sets, 256, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack, grid, vt_grid, *vt);
+    else
+        k_query_rows<<<dim3(grid, num_sets), 256, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
     return mssvt_launch_status();
+}
+
+extern "C" int mssvt_plan_order_multi(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid,
+                                      const int *host_nq, const float *const *host_qmeta, int win_capacity,
+                                      int row_capacity, int *const *host_perm, int *const *host_num_active,
+                                      int *const *host_q_off, float *const *host_qrow_meta,
+                                      int *const *host_qrow_src, int *const *host_num_rows, void *stream) {
+    return mssvt_plan_order_multi_vt(num_sets, num_wins_dev, host_nq_valid, host_nq, host_qmeta, win_capacity, row_capacity, host_perm,
+                                     host_num_active, host_q_off, host_qrow_meta, host_qrow_src, host_num_rows, nullptr, stream);
 }
 
 extern "C" int mssvt_plan_order(const int *num_wins_dev, const int *nq_valid, int nq, const float *qmeta,
