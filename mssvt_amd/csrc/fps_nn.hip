@@ -11,6 +11,9 @@
 // tree is replayed level by level (LDS for strides >= 64, __shfl_down below) so
 // that every arg-max TIE resolves to the same index the CUDA block would pick
 // (ties are the norm: the inputs are small integer offsets plus zero padding).
+// Four waves share a workgroup, so the dynamic LDS request is 16 * ((4 n + tree + 3) & ~3) bytes (tree = 2 bs floats if
+// bs > 64): up to 96 KB with the points in LDS (n <= 1024), and from n = 769 on it passes 64 KB, where the launch first
+// raises the kernel's dynamic LDS limit.  Longer inputs keep points and distances in global memory and only the tree in LDS.
 //
 // K9 replaces three_nn_kernel_fast (ref: .../interpolate_gpu.cu:16-59): one lane
 // per unknown point, the known points are read with wave-uniform (broadcast)
@@ -134,8 +137,14 @@ extern "C" int mssvt_farthest_point_sampling(int b, int n, int m, const float *d
     const bool in_lds = (size_t)per_wave * sizeof(float) * FPS_WPB <= 96 * 1024;
     const int grid = divup(b, FPS_WPB);
     if (in_lds) {
-        k_fps<true><<<grid, FPS_WPB * MSSVT_WAVE, (size_t)per_wave * sizeof(float) * FPS_WPB,
-                      (hipStream_t)stream>>>(b, n, m, bs, dataset, temp, idxs, per_wave);
+        const size_t lds_bytes = (size_t)per_wave * sizeof(float) * FPS_WPB;  // 64 KB is passed at n = 769
+        if (lds_bytes > 64 * 1024) {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_fps<true>),
+                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+            if (e != hipSuccess) return (int)e;
+        }
+        k_fps<true><<<grid, FPS_WPB * MSSVT_WAVE, lds_bytes, (hipStream_t)stream>>>(b, n, m, bs, dataset, temp, idxs,
+                                                                                    per_wave);
     } else {
         per_wave = (tree_floats + 3) & ~3;
         k_fps<false><<<grid, FPS_WPB * MSSVT_WAVE, (size_t)per_wave * sizeof(float) * FPS_WPB,

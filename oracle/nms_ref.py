@@ -6,7 +6,9 @@ numpy (float32) restatement of pcdet/ops/iou3d_nms/src/iou3d_nms_kernel.cu:
     1e-2 margin (``check_in_box2d`` :50-61), bubble sort by ``atan2`` around the mean point (:98-100,:178-187), fan area;
   * ``iou_bev``      :209-217  -- overlap / max(sa + sb - overlap, 1e-8);
   * ``nms_kernel`` + the host loop of ``nms_gpu`` (:236-278, iou3d_nms.cpp:90-135): boxes in descending score order,
-    a box suppresses every LATER box whose IoU exceeds the threshold (strict >), greedy keep.
+    a box suppresses every LATER box whose IoU exceeds the threshold (strict >), greedy keep (``nms``: every pair;
+    ``nms_sparse``: the same walk over the pairs that can overlap at all, for thousands of boxes);
+  * ``nms_normal``   :314-372 + iou3d_nms.cpp:138-188 -- the same walk over the axis-aligned IoU.
 Parity status: "parity unpinned" against real CUDA output (no nvcc / NVIDIA GPU here, the reference ships no vectors);
 pinned to hand-derived cases (identical boxes, disjoint boxes, axis-aligned overlaps with known areas) in tests/.
 """
@@ -113,4 +115,56 @@ def nms(boxes, scores, thresh, pre_maxsize=None):
         for j in range(i + 1, n):
             if not removed[j] and iou_bev(b[i], b[j]) > F(thresh):
                 removed[j] = True
+    return order[np.array(keep, dtype=np.int64)]
+
+
+def nms_sparse(boxes, scores, thresh, pre_maxsize=None):
+    """`nms` for thousands of boxes: the same greedy walk, but a kept box meets only the later, not yet removed boxes
+    whose centre is no further away than the two half-diagonals allow (+ 0.02 each, which covers the 1e-2 in-box margin
+    on both sides; float64).  Every other pair has no crossing edges and no corner inside the other box, so its overlap
+    is exactly 0 and it cannot exceed any thresh > 0: the result is `nms`'s."""
+    assert thresh > 0
+    boxes = np.asarray(boxes, F)
+    order = np.argsort(-np.asarray(scores, np.float64), kind="stable")
+    if pre_maxsize is not None:
+        order = order[:pre_maxsize]
+    b = boxes[order]
+    n = b.shape[0]
+    x, y = b[:, 0].astype(np.float64), b[:, 1].astype(np.float64)
+    reach = 0.5 * np.hypot(b[:, 3].astype(np.float64), b[:, 4].astype(np.float64)) + 0.02
+    removed = np.zeros(n, bool)
+    keep = []
+    for i in range(n):
+        if removed[i]:
+            continue
+        keep.append(i)
+        near = np.hypot(x[i + 1:] - x[i], y[i + 1:] - y[i]) <= reach[i] + reach[i + 1:]
+        for j in np.flatnonzero(near & ~removed[i + 1:]) + (i + 1):
+            if iou_bev(b[i], b[j]) > F(thresh):
+                removed[j] = True
+    return order[np.array(keep, dtype=np.int64)]
+
+
+def nms_normal(boxes, scores, thresh):
+    """iou3d_nms_utils.nms_normal_gpu (:101-116): greedy NMS over the axis-aligned BEV IoU of iou_normal
+    (iou3d_nms_kernel.cu:314-325, float32), one vectorised row per kept box -- never an (n, n) matrix."""
+    boxes = np.asarray(boxes, F)
+    order = np.argsort(-np.asarray(scores, np.float64), kind="stable")
+    b = boxes[order]
+    n = b.shape[0]
+    x_lo, x_hi = b[:, 0] - b[:, 3] / F(2), b[:, 0] + b[:, 3] / F(2)
+    y_lo, y_hi = b[:, 1] - b[:, 4] / F(2), b[:, 1] + b[:, 4] / F(2)
+    area = b[:, 3] * b[:, 4]
+    removed = np.zeros(n, bool)
+    keep = []
+    for i in range(n):
+        if removed[i]:
+            continue
+        keep.append(i)
+        s = slice(i + 1, n)
+        left, right = np.maximum(x_lo[i], x_lo[s]), np.minimum(x_hi[i], x_hi[s])
+        top, bottom = np.maximum(y_lo[i], y_lo[s]), np.minimum(y_hi[i], y_hi[s])
+        inter = np.maximum(right - left, F(0)) * np.maximum(bottom - top, F(0))
+        iou = inter / np.maximum(area[i] + area[s] - inter, EPS)
+        removed[s] |= iou > F(thresh)
     return order[np.array(keep, dtype=np.int64)]

@@ -63,6 +63,32 @@ def test_argument_errors_of_the_new_entry_points_are_status_codes():
     assert lib.mssvt_hip_abi_version() == 100
 
 
+def test_nms_sparse_keeps_what_the_all_pairs_oracle_keeps():
+    """nms_ref.nms_sparse (only pairs whose centres are within reach) against nms_ref.nms (every pair), on the cases of
+    tests/test_detector_gpu.py::test_hip_nms_keeps_what_the_oracle_keeps, with and without pre_maxsize."""
+    from tests.test_detector_gpu import _random_boxes
+    for n, thresh, seed in [(1, 0.5, 0), (70, 0.1, 1), (130, 0.5, 2), (130, 0.7, 3), (193, 0.25, 4)]:
+        bx, scores = _random_boxes(n, seed)
+        for pre in (None, 40):
+            want = nms_ref.nms(bx, scores, thresh, pre)
+            got = nms_ref.nms_sparse(bx, scores, thresh, pre)
+            assert got.dtype == want.dtype and got.tolist() == want.tolist(), (n, thresh, seed, pre)
+        if n > 1:
+            assert 1 < len(want) < min(n, 40)  # pre_maxsize = 40: boxes are kept and boxes are removed
+
+
+def test_nms_normal_oracle_keeps_what_greedy_nms_over_the_iou_normal_matrix_keeps():
+    """nms_ref.nms_normal (one row per kept box) against the greedy walk over the whole iou_normal matrix, on the cases
+    of tests/test_box_iou_gpu.py::test_nms_normal_keeps_what_greedy_nms_over_iou_normal_keeps."""
+    from tests.test_box_iou_gpu import _random_boxes, greedy_nms, iou_normal_np
+    for n, thresh, seed in [(1, 0.5, 0), (130, 0.5, 2), (193, 0.25, 4)]:
+        bx, scores = _random_boxes(n, seed)
+        want = greedy_nms(iou_normal_np(bx, bx), scores, thresh)
+        assert nms_ref.nms_normal(bx, scores, thresh).tolist() == want, (n, thresh, seed)
+        if n > 1:
+            assert 1 < len(want) < n
+
+
 A = [0, 0, 0, 4, 2, 1.5, 0]
 
 
