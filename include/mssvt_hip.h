@@ -330,7 +330,9 @@ int mssvt_occupancy_columns(const int *indices, int num_voxels, int batch_size, 
  *   qrow_meta (rows,4)  per compact row: the slot's qmeta entry (rel.xyz, bits(feature row));
  *   qrow_src (rows,2)   per compact row: (window, attn row = window * nq + slot);
  *   num_rows_dev        total rows (<= num_voxels: the query lists of one pattern are
- *                       disjoint); rows beyond row_capacity are dropped.                  */
+ *                       disjoint).  A window whose rows end beyond row_capacity is dropped
+ *                       whole, with every window behind it: num_rows_dev = its first row,
+ *                       and the attention writes none of its rows.                         */
 int mssvt_plan_order(const int *num_wins_dev, const int *nq_valid, int nq, const float *qmeta,
                      int win_capacity, int row_capacity, int *perm, int *num_active_dev, int *q_off,
                      float *qrow_meta, int *qrow_src, int *num_rows_dev, void *stream);

@@ -1041,7 +1041,8 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
         }
         if (gidx == 0 && lane == MSSVT_WAVE - 1) {
             *num_active = incl;
-            *num_rows = rows_all < row_capacity ? rows_all : row_capacity;  // rows past the capacity are dropped (caller's bound)
+            // past the capacity (caller's bound) pass 1 leaves the first row of the first window that does not fit
+            if (rows_all <= row_capacity) *num_rows = rows_all;
         }
     }
     __syncthreads();
@@ -1065,7 +1066,12 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
                 if (lane >= off) incl += t;
             }
             if (v[u] >= 0) {
-                q_off[w] = carry + incl - val;
+                const int first = carry + incl - val;
+                q_off[w] = first;
+                // A window whose rows end past the capacity is dropped WHOLE, and every window behind it with it (the
+                // attention launches skip them): the row-tiled launches must not see the rows of its that do fit -- they
+                // would turn a Qt row no window launch replaced into an attention row.  Exactly one window straddles the end.
+                if (first <= row_capacity && first + val > row_capacity) *num_rows = first;
                 const int k = min(v[u], max_key);
                 if (k > 0) perm[key_base[k] + atomicAdd(&hist[wv][k], 1)] = w;
             }
