@@ -6,12 +6,14 @@ plus the current torch HIP stream -- torch is only the allocator / stream owner.
 """
 import ctypes
 import os
+import re
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # MSSVT_LIB: another build of the same library (the schedule variants of mssvt_amd/build.py, for the hazard test)
 LIB_PATH = os.environ.get("MSSVT_LIB") or os.path.join(_HERE, "lib", "libmssvt_hip.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mssvt_hip.h")
 
 _lib = None
 
@@ -28,32 +30,20 @@ def lib():
                 "libmssvt_hip.so not built (%s). Run `python -m mssvt_amd.build`; there is no "
                 "CPU fallback for the MsSVT hot path." % LIB_PATH)
         lib_ = ctypes.CDLL(LIB_PATH)
-        lib_.mssvt_hip_status_string.restype = ctypes.c_char_p
-        for name in ("mssvt_hash_workspace_ints", "mssvt_nms_workspace_bytes", "mssvt_linear_wgrad_workspace_floats",
-                     "mssvt_csr_transpose_workspace_bytes", "mssvt_ffn_packed_bytes", "mssvt_level_sorted_scratch_ints",
-                     "mssvt_attn_packed_bytes", "mssvt_frame_workspace_bytes", "mssvt_compress_ws_packed_bytes",
-                     "mssvt_train_tok_slab_floats"):
-            getattr(lib_, name).restype = ctypes.c_longlong
-        global TYPED
-        TYPED = _declare(lib_)
+        _declare(lib_)
         _lib = lib_  # only a fully declared library is cached
     return _lib
 
 
-_NULL = ctypes.c_void_p(0)
-TYPED = False  # argtypes of every entry point set from include/mssvt_hip.h: callers may pass plain ints / floats / addresses
-
-
 def _declare(lib_):
     """argtypes / restype of every `mssvt_*` function from the declarations of include/mssvt_hip.h (int, float,
-    long long, pointers).  With them ctypes converts plain Python ints and floats in C: the fused forward passes ~600
-    scalar / pointer arguments per frame, and a ctypes.c_int / c_void_p object per argument cost ~0.1 ms of host time per
-    frame.  Without the header (a stripped install) nothing is declared and the callers keep wrapping."""
-    import re
-    path = os.path.join(os.path.dirname(_HERE), "include", "mssvt_hip.h")
-    if not os.path.exists(path):
-        return False
-    with open(path) as f:
+    long long, pointers).  With them ctypes converts plain Python ints, floats and addresses in C and refuses a float
+    where C takes an int: callers pass plain values, never ctypes.c_int / c_void_p objects (the fused forward hands over
+    ~600 scalars and pointers per frame).  A missing header or a parameter type unknown here is an error, so no entry
+    point of the header stays undeclared."""
+    if not os.path.exists(HEADER_PATH):
+        raise MssvtHipError("%s not found: the argument types of libmssvt_hip.so are declared from it" % HEADER_PATH)
+    with open(HEADER_PATH) as f:
         txt = f.read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     txt = re.sub(r"//[^\n]*", "", txt)
@@ -62,17 +52,16 @@ def _declare(lib_):
     for ret, name, params in re.findall(r"\b(int|long long|const char \*)\s*(mssvt_\w+)\s*\(([^;{]*?)\)\s*;", txt, flags=re.S):
         fn = getattr(lib_, name, None)
         if fn is None:
-            continue
+            continue  # declared but not exported by this build (tests/test_abi_cpu.py holds the shipped library to the header)
         params = params.replace("\n", " ").strip()
         args = []
         for q in ([] if params in ("", "void") else params.split(",")):
             q = q.strip()
             args.append(ctypes.c_void_p if "*" in q else kinds.get(" ".join(q.split()[:-1])))
         if None in args:
-            continue  # a parameter type this parser does not know: leave the function undeclared (callers wrap)
+            raise MssvtHipError("%s: cannot type parameter %d of %s (`%s`)" % (HEADER_PATH, args.index(None), name, params))
         fn.argtypes = args
         fn.restype = rets[ret]
-    return True
 
 
 def check(status, what):
@@ -82,29 +71,29 @@ def check(status, what):
 
 
 def ptr(t):
-    """Device pointer of a contiguous CUDA(HIP) tensor (None -> NULL)."""
+    """Address of a contiguous CUDA(HIP) tensor as a plain int (None -> NULL)."""
     if t is None:
-        return _NULL
+        return None
     if not (t.is_cuda and t.is_contiguous()):
         raise MssvtHipError("mssvt_amd ops need contiguous tensors on the GPU (no CPU path)")
-    return ctypes.c_void_p(t.data_ptr())
+    return t.data_ptr()
 
 
-def ptr_fast(t):
+def addr(t):
     """`ptr` without the device / contiguity checks: for buffers the fused path allocated itself and for module
     parameters (the frame's front is launch bound: ~200 pointer conversions per frame)."""
-    return _NULL if t is None else ctypes.c_void_p(t.data_ptr())
-
-
-def ptr_raw(t):
-    """Address of a device buffer as a plain int (None -> NULL): for entry points with declared argtypes."""
     return None if t is None else t.data_ptr()
 
 
+def f3(xs):
+    """Host array of three floats (voxel size, range minimum, window size in metres)."""
+    return (ctypes.c_float * 3)(*[float(v) for v in xs])
+
+
 def stream():
-    """Raw handle of torch's current HIP stream (the fast C accessor: torch.cuda.current_stream()
+    """Raw handle of torch's current HIP stream as a plain int (the fast C accessor: torch.cuda.current_stream()
     builds a Python Stream object, ~8 us per call, 20+ calls per forward)."""
-    return ctypes.c_void_p(torch._C._cuda_getCurrentRawStream(torch.cuda.current_device()))
+    return torch._C._cuda_getCurrentRawStream(torch.cuda.current_device())
 
 
 _fns = {}
@@ -113,7 +102,10 @@ _fns = {}
 def call(name, *args):
     fn = _fns.get(name)
     if fn is None:
-        fn = _fns[name] = getattr(lib(), name)
+        fn = getattr(lib(), name)
+        if fn.argtypes is None:  # exported but not in the header: a plain-int address would be cut to 32 bits
+            raise MssvtHipError("%s is not declared in include/mssvt_hip.h: set its argtypes and call it through lib()" % name)
+        _fns[name] = fn
     status = fn(*args)
     if status != 0:
         check(status, name)

@@ -12,14 +12,11 @@ BatchNorm1d sees exactly the reference's rows (dynamic_vfe.py:85-91), the per-vo
 per-voxel max a ``scatter_reduce('amax')`` (gradient to the maximal rows; pinned to a training step of the reference's
 module by tests/golden/dynamic_vfe_train_*.npz: output, every parameter gradient, the BatchNorm buffers).
 """
-import ctypes
-
 import torch
 from torch import nn
 
 from . import _lib, voxelize
 
-_i = ctypes.c_int
 # the fused PFN of the default DynamicVFE configuration (csrc/pfn_fused.hip) over points grouped by voxel (csrc/pfn_sorted.hip:
 # no atomics on feature rows, no fills, x2 never stored); False: the atomic reductions of round 5 (kept: the comparator of
 # tests/test_vfe_gpu.py)
@@ -33,8 +30,8 @@ def voxel_mean_xyz(points, point_voxel, num_voxels):
     mean = torch.empty((max(num_voxels, 1), 3), dtype=torch.float32, device=dev)
     cnt = torch.empty(max(num_voxels, 1), dtype=torch.int32, device=dev)
     scratch = torch.empty(max(num_voxels, 1) * 3, dtype=torch.int64, device=dev)
-    _lib.call("mssvt_voxel_mean_xyz", _lib.ptr(points), _i(stride), ctypes.c_longlong(P), _lib.ptr(point_voxel),
-              _i(num_voxels), _lib.ptr(mean), _lib.ptr(cnt), _lib.ptr(scratch), _lib.stream())
+    _lib.call("mssvt_voxel_mean_xyz", _lib.ptr(points), stride, P, _lib.ptr(point_voxel),
+              num_voxels, _lib.ptr(mean), _lib.ptr(cnt), _lib.ptr(scratch), _lib.stream())
     return mean[:num_voxels], cnt[:num_voxels]
 
 
@@ -43,8 +40,8 @@ def voxel_max(features, point_voxel, num_voxels):
     features = features.contiguous()
     P, F = features.shape
     out = torch.empty((max(num_voxels, 1), F), dtype=torch.float32, device=features.device)
-    _lib.call("mssvt_voxel_max", _lib.ptr(features), _i(F), ctypes.c_longlong(P), _lib.ptr(point_voxel),
-              _i(num_voxels), _lib.ptr(out), _lib.stream())
+    _lib.call("mssvt_voxel_max", _lib.ptr(features), F, P, _lib.ptr(point_voxel),
+              num_voxels, _lib.ptr(out), _lib.stream())
     return out[:num_voxels]
 
 
@@ -149,21 +146,18 @@ class DynamicVFE(nn.Module):
         N = voxel_coords.shape[0]
         if N and self._fused_pfn_ok(points) and SORTED_PFN:
             P, dev = points.shape[0], points.device
-            lib = _lib.lib()
-            lib.mssvt_pfn_sorted_workspace_ints.restype = ctypes.c_longlong
-            ws = torch.empty(int(lib.mssvt_pfn_sorted_workspace_ints(ctypes.c_longlong(P), _i(N))), dtype=torch.int32, device=dev)
+            ws = torch.empty(int(_lib.lib().mssvt_pfn_sorted_workspace_ints(P, N)), dtype=torch.int32, device=dev)
             x1 = torch.empty((P, 64), dtype=torch.float32, device=dev)
             m1 = torch.empty((N, 64), dtype=torch.float32, device=dev)
             out = torch.empty((N, 128), dtype=torch.float32, device=dev)
             (l1, n1), (l2, n2) = (self.pfn[0][0], self.pfn[0][1]), (self.pfn[1][0], self.pfn[1][1])
-            f3 = lambda xs: (ctypes.c_float * 3)(*[float(v) for v in xs])  # noqa: E731
             vc = voxel_coords.contiguous()
-            _lib.call("mssvt_pfn_sorted_64_128", _lib.ptr(points), _i(points.shape[1]), ctypes.c_longlong(P), _lib.ptr(pv), _i(N),
-                      _lib.ptr(vc), f3(self.voxel_size_l),
-                      f3([self.voxel_size_l[k] / 2 + self.point_cloud_range_l[k] for k in range(3)]),
+            _lib.call("mssvt_pfn_sorted_64_128", _lib.ptr(points), points.shape[1], P, _lib.ptr(pv), N,
+                      _lib.ptr(vc), _lib.f3(self.voxel_size_l),
+                      _lib.f3([self.voxel_size_l[k] / 2 + self.point_cloud_range_l[k] for k in range(3)]),
                       _lib.ptr(l1.weight), _lib.ptr(l1.bias), _lib.ptr(n1.weight), _lib.ptr(n1.bias), _lib.ptr(n1.running_mean),
-                      _lib.ptr(n1.running_var), ctypes.c_float(n1.eps), _lib.ptr(l2.weight), _lib.ptr(l2.bias), _lib.ptr(n2.weight),
-                      _lib.ptr(n2.bias), _lib.ptr(n2.running_mean), _lib.ptr(n2.running_var), ctypes.c_float(n2.eps),
+                      _lib.ptr(n1.running_var), n1.eps, _lib.ptr(l2.weight), _lib.ptr(l2.bias), _lib.ptr(n2.weight),
+                      _lib.ptr(n2.bias), _lib.ptr(n2.running_mean), _lib.ptr(n2.running_var), n2.eps,
                       _lib.ptr(ws), _lib.ptr(x1), _lib.ptr(m1), _lib.ptr(out), _lib.stream())
             batch_dict['voxel_features'] = out
             batch_dict['voxel_coords'] = vc
@@ -176,14 +170,13 @@ class DynamicVFE(nn.Module):
             x2 = torch.empty((P, 128), dtype=torch.float32, device=dev)
             out = torch.empty((N, 128), dtype=torch.float32, device=dev)
             (l1, n1), (l2, n2) = (self.pfn[0][0], self.pfn[0][1]), (self.pfn[1][0], self.pfn[1][1])
-            f3 = lambda xs: (ctypes.c_float * 3)(*[float(v) for v in xs])  # noqa: E731
             vc = voxel_coords.contiguous()
-            _lib.call("mssvt_pfn_fused_64_128", _lib.ptr(points), _i(points.shape[1]), ctypes.c_longlong(P), _lib.ptr(pv), _i(N),
-                      _lib.ptr(xyz_mean), _lib.ptr(vc), f3(self.voxel_size_l),
-                      f3([self.voxel_size_l[k] / 2 + self.point_cloud_range_l[k] for k in range(3)]),
+            _lib.call("mssvt_pfn_fused_64_128", _lib.ptr(points), points.shape[1], P, _lib.ptr(pv), N,
+                      _lib.ptr(xyz_mean), _lib.ptr(vc), _lib.f3(self.voxel_size_l),
+                      _lib.f3([self.voxel_size_l[k] / 2 + self.point_cloud_range_l[k] for k in range(3)]),
                       _lib.ptr(l1.weight), _lib.ptr(l1.bias), _lib.ptr(n1.weight), _lib.ptr(n1.bias), _lib.ptr(n1.running_mean),
-                      _lib.ptr(n1.running_var), ctypes.c_float(n1.eps), _lib.ptr(l2.weight), _lib.ptr(l2.bias), _lib.ptr(n2.weight),
-                      _lib.ptr(n2.bias), _lib.ptr(n2.running_mean), _lib.ptr(n2.running_var), ctypes.c_float(n2.eps),
+                      _lib.ptr(n1.running_var), n1.eps, _lib.ptr(l2.weight), _lib.ptr(l2.bias), _lib.ptr(n2.weight),
+                      _lib.ptr(n2.bias), _lib.ptr(n2.running_mean), _lib.ptr(n2.running_var), n2.eps,
                       _lib.ptr(x1), _lib.ptr(m1), _lib.ptr(x2), _lib.ptr(out), _lib.stream())
             batch_dict['voxel_features'] = out
             batch_dict['voxel_coords'] = vc

@@ -135,7 +135,7 @@ def _build(net, dev, batch_size):
     i3 = lambda xs: (ctypes.c_int * len(xs))(*[int(v) for v in xs])  # noqa: E731
     _lib.call("mssvt_frame_set_level", fr.handle, int(batch_size), X, Y, Z, int(net.hash_size), f3(net.voxel_size),
               f3(net.point_cloud_range), C, FF)
-    P = fused._P
+    P = _lib.addr
     for blk in body:
         if getattr(blk, "impl", None) != "fused" or getattr(blk, "ffn_arith", fused.FFN_ARITH) != "f16x3":
             return _no("a Block with impl != 'fused' or ffn_arith != 'f16x3'", None)
@@ -270,7 +270,6 @@ def forward(net, feats, coords, batch_size, defer=False):
     if n <= 0 or coords.shape[0] != n:
         return None
     cur = _lib.stream()
-    cur = getattr(cur, "value", cur) or 0
     fr = _state(net, feats, batch_size, cur)
     if fr is None:
         return _declined(net, net.__dict__["_frame_state"].get("why") or "not eligible")
@@ -295,7 +294,7 @@ def forward(net, feats, coords, batch_size, defer=False):
     out_t = torch.empty((B, H, 2), dtype=torch.int32, device=dev)
     out_c = torch.empty((B,), dtype=torch.int32, device=dev)
     _lib.call("mssvt_frame_forward", fr.handle, n, feats.data_ptr(), indices.data_ptr(), ws.data_ptr(), ws.numel(),
-              out_f.data_ptr(), out_i.data_ptr(), out_t.data_ptr(), out_c.data_ptr(), _lib.stream())
+              out_f.data_ptr(), out_i.data_ptr(), out_t.data_ptr(), out_c.data_ptr(), cur)
     if defer:
         return Pending(net, fr, (out_f, out_i, out_t, out_c), batch_size, H)
     return _finish(net, fr, (out_f, out_i, out_t, out_c), batch_size, H)

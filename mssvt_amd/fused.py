@@ -27,14 +27,10 @@ import torch
 import torch.nn.functional as F
 
 from . import _lib, mssvt_ops
+from ._lib import addr  # every tensor handed over here is a contiguous device buffer (allocated below, or a parameter)
 from .mssvt_utils import batch_counts
 
-try:
-    _lib.lib()
-except _lib.MssvtHipError:  # library not built: the first entry-point call raises (there is no CPU fallback)
-    pass
-# scalars and addresses go to the C entry points as plain Python values when their argtypes are declared (_lib.TYPED)
-_i, _f = (int, float) if _lib.TYPED else (ctypes.c_int, ctypes.c_float)
+
 def _no_grad(fn):
     """torch.no_grad() as a decorator without its per-call cost when autograd is already off (the inference path enters ~30
     decorated functions per frame; each torch.no_grad() entry clones the context object and flips the grad mode twice)."""
@@ -45,13 +41,6 @@ def _no_grad(fn):
         return fn(*args, **kwargs)
     wrapper.__name__, wrapper.__doc__ = fn.__name__, fn.__doc__
     return wrapper
-
-
-_P = _lib.ptr_raw if _lib.TYPED else _lib.ptr_fast  # every tensor handed over here is a contiguous device buffer (allocated below, or a parameter)
-
-
-def _f3(xs):
-    return (ctypes.c_float * 3)(*[float(v) for v in xs])
 
 
 class _Plan(object):
@@ -181,7 +170,7 @@ def _sorted_level(blocks, indices, B, H, spatial_shape, early_readback=False):
             shapes=ints_([[[X, Y, Z][i] // b.win1_size[i] for i in range(3)] for b in todo]),
             wsizes=ints_([b.win1_size for b in todo]),
             maxw=(ctypes.c_int * max(k, 1))(*[int(b.max_num_wins) for b in todo]),
-            scratch=int(_lib.lib().mssvt_level_sorted_scratch_ints(_i(B), _i(X), _i(Y))))
+            scratch=int(_lib.lib().mssvt_level_sorted_scratch_ints(B, X, Y)))
     todo, k, sizes, offs = static["todo"], static["k"], static["sizes"], static["offs"]
     # zeroed together with the frame's -1 arena when there is one (FillArena.take_zero), else cleared by the call itself
     arena = mssvt_ops.FillArena.current
@@ -201,10 +190,10 @@ def _sorted_level(blocks, indices, B, H, spatial_shape, early_readback=False):
     wins = [torch.empty((n, 4), dtype=torch.int32, device=dev) for _ in range(k)]
     vcounts = zero[offs[5]:offs[5] + max(k, 1) * B].view(max(k, 1), B)
     ptrs = lambda ts: (ctypes.c_void_p * max(k, 1))(*[0 if t is None else t.data_ptr() for t in ts])  # noqa: E731
-    _lib.call("mssvt_level_setup_sorted", _i(n), _i(B), _i(X), _i(Y), _i(Z), _i(H), _P(indices), _P(zero),
-              ctypes.c_longlong(-zero.numel() * 4 if precleared else zero.numel() * 4), _P(cnt), _P(start), _P(occ), _P(vbase),
-              _P(status), _i(k), static["shapes"], static["wsizes"], static["maxw"], ptrs(wins), ptrs(tables),
-              ptrs([vcounts[i] for i in range(k)]), ptrs(hdrs), _P(scratch), _lib.stream())
+    _lib.call("mssvt_level_setup_sorted", n, B, X, Y, Z, H, addr(indices), addr(zero),
+              -zero.numel() * 4 if precleared else zero.numel() * 4, addr(cnt), addr(start), addr(occ), addr(vbase),
+              addr(status), k, static["shapes"], static["wsizes"], static["maxw"], ptrs(wins), ptrs(tables),
+              ptrs([vcounts[i] for i in range(k)]), ptrs(hdrs), addr(scratch), _lib.stream())
     st = {"indices": indices, "v_bs_cnt": cnt, "plans": {}, "occ": occ, "vbase": vbase, "level_status": status,
           "sorted": True, "status_words": [status], "_zero": zero,
           "partitions": {_partition_key(b): (wins[i], tables[i], vcounts[i], hdrs[i]) for i, b in enumerate(todo)}}
@@ -289,7 +278,7 @@ def setup_input_level(blocks, sp_kwargs, assume_sorted=True):
     k = len(todo)
     use_occ = OCC_COLUMNS and Z <= 64
     al = lambda v: (int(v) + 63) // 64 * 64  # noqa: E731  (256-byte aligned pieces)
-    stride = al(_lib.lib().mssvt_hash_workspace_ints(_i(n), _i(B)))
+    stride = al(_lib.lib().mssvt_hash_workspace_ints(n, B))
     sizes = [al(B), stride, k * stride, al(2 * B * X * Y) if use_occ else 0]
     zero = torch.empty(sum(sizes), dtype=torch.int32, device=dev)  # cleared by the call itself
     offs = [sum(sizes[:i]) for i in range(len(sizes))]
@@ -305,11 +294,11 @@ def setup_input_level(blocks, sp_kwargs, assume_sorted=True):
     shapes = [[[X, Y, Z][i] // b.win1_size[i] for i in range(3)] for b in todo]
     ints = lambda rows: (ctypes.c_int * max(3 * k, 1))(*[int(v) for r in rows for v in r])  # noqa: E731
     ptrs = lambda ts: (ctypes.c_void_p * max(k, 1))(*[t.data_ptr() for t in ts])  # noqa: E731
-    _lib.call("mssvt_level_setup", _i(n), _i(B), _i(X), _i(Y), _i(Z), _i(H), _P(indices), _P(zero),
-              ctypes.c_longlong(zero.numel() * 4), _P(cnt), _P(table), _P(map_ws), _P(occ),
-              _i(k), ints(shapes), ints([b.win1_size for b in todo]),
+    _lib.call("mssvt_level_setup", n, B, X, Y, Z, H, addr(indices), addr(zero),
+              zero.numel() * 4, addr(cnt), addr(table), addr(map_ws), addr(occ),
+              k, ints(shapes), ints([b.win1_size for b in todo]),
               (ctypes.c_int * max(k, 1))(*[int(b.max_num_wins) for b in todo]), ptrs(wins), ptrs(tables),
-              ptrs(scratch), ptrs([vcounts[i] for i in range(k)]), _P(part_ws), ctypes.c_longlong(stride),
+              ptrs(scratch), ptrs([vcounts[i] for i in range(k)]), addr(part_ws), stride,
               _lib.stream())
     sp = SparseTensor(map_table=table, **sp_kwargs)
     sp.v_bs_cnt, sp._cnt_of, sp.map_status = cnt, sp.indices, map_ws[0:1]
@@ -326,8 +315,8 @@ def occupancy_columns(sp, st):
         occ = None
         if OCC_COLUMNS and Z <= 64:
             occ = torch.empty(sp.batch_size * X * Y, dtype=torch.int64, device=sp.indices.device)
-            _lib.call("mssvt_occupancy_columns", _P(sp.indices), _i(sp.indices.shape[0]), _i(sp.batch_size),
-                      _i(X), _i(Y), _i(Z), _P(occ), _lib.stream())
+            _lib.call("mssvt_occupancy_columns", addr(sp.indices), sp.indices.shape[0], sp.batch_size,
+                      X, Y, Z, addr(occ), _lib.stream())
         st["occ"] = occ
     return st["occ"]
 
@@ -349,7 +338,7 @@ def _lists_disjoint(block):
 def _plan_tables(block, sp, p, key, dev, N):
     """ctypes arguments (num_tabs, lists, interps, zero rows, tab_row / tab_w pointers) of mssvt_window_plan_two for the
     (query list, interpolation) variants of the Blocks that share the plan, and their keys in p.tables."""
-    none = (_i(0), None, None, None, None, None)
+    none = (0, None, None, None, None, None)
     p.tables = {}
     group = [b for b in (getattr(sp, "_plan_group", None) or [block]) if b.plan_key() == key and supported(b, sp)]
     if not group or not _lists_disjoint(block):
@@ -370,7 +359,7 @@ def _plan_tables(block, sp, p, key, dev, N):
     ia = lambda v: (ctypes.c_int * n)(*[int(x) for x in v])  # noqa: E731
     pa = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
     lists = [{1: 0, 0: 1, 2: 2}[k[0]] for _, k in todo]  # cbs_pattern -> list: 1 odd, 0 even, 2 win1
-    args = (_i(n), ia(lists), ia([k[1] for _, k in todo]), ia([p.attn_zero[(k[2], k[3])] for _, k in todo]),
+    args = (n, ia(lists), ia([k[1] for _, k in todo]), ia([p.attn_zero[(k[2], k[3])] for _, k in todo]),
             pa([p._tab_rows[i] for i in range(n)]), pa([p._tab_ws[i] for i in range(n)]))
     return args, [k for _, k in todo]
 
@@ -453,19 +442,19 @@ def two_scale_plan(block, sp, all_lists=False):
     if occ is not None and fp4[2] * fp4[3] > 1024:
         occ = None  # footprint beyond the plan kernel's column tile: it probes the hash instead
     p._plan_args = (  # raw pointers / sizes only (tools/time_plan.py launches the kernel alone with them)
-              *[_i(int(v)) for v in sp.spatial_shape],
-              *[_i(int(v)) for v in block.win1_size], _i(n_o), _i(n_e), _i(n1), _i(n2), _i(H), _i(B),
-              _i(t['odd'].shape[0]), _i(t['even'].shape[0]), _i(t['win1'].shape[0]), _i(t['win2'].shape[0]),
-              _P(t['odd']), _P(t['even']), _P(t['win1']), _P(t['win2']), _i(K),
-              _P(p.win_ind), _P(p.num_wins), _i(cap), _P(_voxel_table(sp, st, occ)),
-              _P(st["v_bs_cnt"]), _P(p.ind_odd), _P(p.ind_even), _P(p.ind_win1),
-              _P(p.k_ind[0]), _P(p.k_ind[1]), _P(p.k_mask[0]), _P(p.k_mask[1]),
-              _P(p.win_vstart), _P(p.owner_win1), _P(p.owner_odd), _P(p.owner_even),
-              _P(sp.indices), _f3(sp.voxel_size), _f3(sp.point_cloud_range[0:3]), _f3(p.win_size_m),
-              _P(p.qmeta_odd), _P(p.qmeta_even), _P(p.qmeta_win1), _P(p.kmeta[0]),
-              _P(p.kmeta[1]), _P(p.wcentre), _P(p.nq_valid), _P(occ),
-              fp4, _P(packed), _P(st.get("vbase") if occ is not None else None),
-              _P(st.get("level_status") if occ is not None else None), _P(p.k_bs_cnt))
+              *[int(v) for v in sp.spatial_shape],
+              *[int(v) for v in block.win1_size], n_o, n_e, n1, n2, H, B,
+              t['odd'].shape[0], t['even'].shape[0], t['win1'].shape[0], t['win2'].shape[0],
+              addr(t['odd']), addr(t['even']), addr(t['win1']), addr(t['win2']), K,
+              addr(p.win_ind), addr(p.num_wins), cap, addr(_voxel_table(sp, st, occ)),
+              addr(st["v_bs_cnt"]), addr(p.ind_odd), addr(p.ind_even), addr(p.ind_win1),
+              addr(p.k_ind[0]), addr(p.k_ind[1]), addr(p.k_mask[0]), addr(p.k_mask[1]),
+              addr(p.win_vstart), addr(p.owner_win1), addr(p.owner_odd), addr(p.owner_even),
+              addr(sp.indices), _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3]), _lib.f3(p.win_size_m),
+              addr(p.qmeta_odd), addr(p.qmeta_even), addr(p.qmeta_win1), addr(p.kmeta[0]),
+              addr(p.kmeta[1]), addr(p.wcentre), addr(p.nq_valid), addr(occ),
+              fp4, addr(packed), addr(st.get("vbase") if occ is not None else None),
+              addr(st.get("level_status") if occ is not None else None), addr(p.k_bs_cnt))
     # the interpolation tables of the Blocks that share this plan: in the same launch when every voxel has ONE owner
     tab_args, tab_keys = _plan_tables(block, sp, p, key, dev, N)
     _lib.call("mssvt_window_plan_two", *p._plan_args, *tab_args, _lib.stream())
@@ -550,9 +539,9 @@ def _work_order(block, p, nq, num_voxels):
                  row_meta=torch.empty((cap_rows, 4), dtype=torch.float32, device=dev),
                  row_src=torch.empty((cap_rows, 2), dtype=torch.int32, device=dev),
                  n_rows=torch.empty(1, dtype=torch.int32, device=dev), row_cap=cap_rows)
-        _lib.call("mssvt_plan_order", _P(p.num_wins), _P(o["nq_valid"]), _i(nq),
-                  _P(_qmeta(block, p)), _i(p.cap), _i(cap_rows), _P(o["perm"]), _P(o["n_act"]),
-                  _P(o["q_off"]), _P(o["row_meta"]), _P(o["row_src"]), _P(o["n_rows"]),
+        _lib.call("mssvt_plan_order", addr(p.num_wins), addr(o["nq_valid"]), nq,
+                  addr(_qmeta(block, p)), p.cap, cap_rows, addr(o["perm"]), addr(o["n_act"]),
+                  addr(o["q_off"]), addr(o["row_meta"]), addr(o["row_src"]), addr(o["n_rows"]),
                   _lib.stream())
         p.orders[pat] = o
     return p.orders[pat]
@@ -655,11 +644,11 @@ def _attn_kv16_ok(block, r, p):
         r["kv16_ok"] = bool(math.isfinite(worst) and worst < FFN_F16_LIMIT)
         r["kv16_packed"] = None
         if r["kv16_ok"] and least >= ATTN_F16_FLOOR:
-            sizes = [int(_lib.lib().mssvt_attn_packed_bytes(_i(int(cg)), _i(r["hd"]))) for cg in r["cg"]]
+            sizes = [int(_lib.lib().mssvt_attn_packed_bytes(int(cg), r["hd"])) for cg in r["cg"]]
             if all(n > 0 for n in sizes):
                 blobs = [torch.empty((n,), dtype=torch.uint8, device=g1.device) for n in sizes]
                 for cg, Wq, Wkv, Wo, blob in zip(r["cg"], r["Wq"], r["Wkv"], r["Wo"], blobs):
-                    _lib.call("mssvt_attn_pack_weights", _i(int(cg)), _i(r["hd"]), _f(r["scale"]),
+                    _lib.call("mssvt_attn_pack_weights", int(cg), r["hd"], r["scale"],
                               _lib.ptr(Wq.detach().contiguous()), _lib.ptr(Wkv.detach().contiguous()),
                               _lib.ptr(Wo.detach().contiguous()), _lib.ptr(blob), _lib.stream())
                 r["kv16_blobs"] = blobs  # keeps the buffers alive
@@ -675,7 +664,7 @@ def _attn_weight_args(r, pa):
     ptrs = tuple(t.data_ptr() for k in ("Wq", "bq", "Wkv", "bkv", "Wo", "bo") for t in r[k]) + (r["Wp"].data_ptr(), r["bp"].data_ptr())
     if w is None or w[0] != ptrs:
         w = r["warg"] = (ptrs, (pa(r["Wq"]), pa(r["bq"]), pa(r["Wkv"]), pa(r["bkv"]), pa(r["Wo"]), pa(r["bo"]),
-                                _P(r["Wp"]), _P(r["bp"])))
+                                addr(r["Wp"]), addr(r["bp"])))
     return w[1]
 
 
@@ -684,17 +673,17 @@ def _attention_call(block, p, od, C, nq, xhat, qbuf, attn, groups=None):
     r = _attn_refs(block, groups)
     n = r["n"]
     pa = lambda ts: (ctypes.c_void_p * n)(*[t.data_ptr() for t in ts])  # noqa: E731
-    head = (_i(C), _i(n), r["c0"], r["cg"], r["heads"], _i(r["hd"]), _f(r["scale"]), _i(nq), _i(r["K"]), _P(xhat),
-            _P(od["n_act"]), _P(od["perm"]), _P(od["q_off"]), _P(od["nq_valid"]), _P(od["n_rows"]), _i(od["row_cap"]),
-            _P(od["row_meta"]), _P(od["row_src"]), pa([p.kmeta[g] for g in r["gs"]]), _P(p.wcentre),
+    head = (C, n, r["c0"], r["cg"], r["heads"], r["hd"], r["scale"], nq, r["K"], addr(xhat),
+            addr(od["n_act"]), addr(od["perm"]), addr(od["q_off"]), addr(od["nq_valid"]), addr(od["n_rows"]), od["row_cap"],
+            addr(od["row_meta"]), addr(od["row_src"]), pa([p.kmeta[g] for g in r["gs"]]), addr(p.wcentre),
             *_attn_weight_args(r, pa))
     if getattr(block, "attn_dtype", "f32") == "bf16" and r["bf16_ok"]:
-        _lib.call("mssvt_block_attention_bf16", *head, _P(attn), _lib.stream())
+        _lib.call("mssvt_block_attention_bf16", *head, addr(attn), _lib.stream())
     elif getattr(block, "attn_kv16", ATTN_KV16) and _attn_kv16_ok(block, r, p):
-        _lib.call("mssvt_block_attention_kv16", *head, _P(qbuf), _P(attn),
+        _lib.call("mssvt_block_attention_kv16", *head, addr(qbuf), addr(attn),
                   r["kv16_packed"] if getattr(block, "attn_qo16", ATTN_QO16) else None, _lib.stream())
     else:
-        _lib.call("mssvt_block_attention", *head, _P(qbuf), _P(attn), _lib.stream())
+        _lib.call("mssvt_block_attention", *head, addr(qbuf), addr(attn), _lib.stream())
 
 
 FFN_SHAPES = {(128, 256), (64, 128), (32, 64)}  # instantiated in csrc/ffn.hip
@@ -748,9 +737,9 @@ def _ffn_f16_weights(fr):
         ok = bool(torch.isfinite(worst).item() and float(worst) < FFN_F16_LIMIT)
         packed = None
         if ok:
-            nbytes = int(_lib.lib().mssvt_ffn_packed_bytes(_i(fr["C"]), _i(fr["FF"])))
+            nbytes = int(_lib.lib().mssvt_ffn_packed_bytes(fr["C"], fr["FF"]))
             packed = torch.empty((nbytes,), dtype=torch.uint8, device=fr["W1"].device)
-            _lib.call("mssvt_ffn_pack_weights", _i(fr["C"]), _i(fr["FF"]), _lib.ptr(fr["W1"].detach().contiguous()),
+            _lib.call("mssvt_ffn_pack_weights", fr["C"], fr["FF"], _lib.ptr(fr["W1"].detach().contiguous()),
                       _lib.ptr(fr["W2"].detach().contiguous()), _lib.ptr(packed), _lib.stream())
         fr["f16_packed"] = packed
         fr["f16_ver"] = ver
@@ -785,19 +774,19 @@ def _ffn_tail(block, sp, x_new, x_in=None, owner=None, table=None, n_rows_dev=No
         # fp32 MFMA: two launches with LDS-resident weights; the hidden activations go through this scratch
         split = phases != 4
         hidden = torch.empty((n, FF), dtype=torch.float32, device=x_new.device) if split else packed
-        tail = (_P(fr["lnw"]), _P(fr["lnb"]), _f(fr["eps"]), _P(fr["W1"]), _P(fr["b1"]), _P(fr["W2"]), _P(fr["b2"]), _P(y),
-                _P(nxt.weight if y_norm is not None else None),
-                _P(nxt.bias if y_norm is not None else None),
-                _f(nxt.eps if y_norm is not None else 0.0), _P(y_norm), _P(hidden),
-                _P(n_rows_dev), _i(phases), _lib.stream())
+        tail = (addr(fr["lnw"]), addr(fr["lnb"]), fr["eps"], addr(fr["W1"]), addr(fr["b1"]), addr(fr["W2"]), addr(fr["b2"]), addr(y),
+                addr(nxt.weight if y_norm is not None else None),
+                addr(nxt.bias if y_norm is not None else None),
+                nxt.eps if y_norm is not None else 0.0, addr(y_norm), addr(hidden),
+                addr(n_rows_dev), phases, _lib.stream())
         def launch(tail_):
             if table is not None:
                 (tab_row, tab_w), attn = table
-                _lib.call("mssvt_ffn_fused_interp", _i(n), _i(C), _i(FF), _P(x_in), _P(tab_row),
-                          _P(tab_w), _P(attn), *tail_)
+                _lib.call("mssvt_ffn_fused_interp", n, C, FF, addr(x_in), addr(tab_row),
+                          addr(tab_w), addr(attn), *tail_)
             else:
-                _lib.call("mssvt_ffn_fused", _i(n), _i(C), _i(FF), _P(x_new), _P(x_in),
-                          _P(owner), *tail_)
+                _lib.call("mssvt_ffn_fused", n, C, FF, addr(x_new), addr(x_in),
+                          addr(owner), *tail_)
 
         if FFN_TIMER is not None and phases == 4:
             # bench.py's live roofline: HIP events around k_ffn_ws inside a repeat of the timed steps
@@ -810,9 +799,9 @@ def _ffn_tail(block, sp, x_new, x_in=None, owner=None, table=None, n_rows_dev=No
             # fp32 arithmetic: k_ffn_up alone (two C calls instead of one: the same two launches, the same stream)
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             e0.record()
-            launch(tail[:-2] + (_i(1), tail[-1]))
+            launch(tail[:-2] + (1, tail[-1]))
             e1.record()
-            launch(tail[:-2] + (_i(2), tail[-1]))
+            launch(tail[:-2] + (2, tail[-1]))
             FFN_TIMER.append(("up", e0, e1, n if n_rows_dev is None else n_rows_dev, C, FF, y_norm is not None))
         else:
             launch(tail)
@@ -839,8 +828,8 @@ def layer_norm(x, norm):
         return F.layer_norm(x, (C,), norm.weight, norm.bias, norm.eps)
     x = x.contiguous()
     y = torch.empty_like(x)
-    _lib.call("mssvt_layer_norm", _P(x), _i(x.shape[0]), _i(C), _P(norm.weight), _P(norm.bias),
-              _f(norm.eps), _P(y), _lib.stream())
+    _lib.call("mssvt_layer_norm", addr(x), x.shape[0], C, addr(norm.weight), addr(norm.bias),
+              norm.eps, addr(y), _lib.stream())
     return y
 
 
@@ -928,7 +917,7 @@ def block_forward(block, sp):
     od = _work_order(block, p, nq, N)
     ma = block.ms_attn
     qbuf = _query_scratch(p, od["row_cap"], ma, x_in.device)
-    vs3, mn3, ws3 = _f3(sp.voxel_size), _f3(sp.point_cloud_range[0:3]), _f3(p.win_size_m)
+    vs3, mn3, ws3 = _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3]), _lib.f3(p.win_size_m)
     _wait_side(sp, "_xhat_event")  # xhat of the frame's first Block comes from the side stream (overlap_front)
     _attention_call(block, p, od, C, nq, xhat, qbuf, attn)
     interp = 1 if block.use_feature_interpolation else 0
@@ -943,9 +932,9 @@ def block_forward(block, sp):
         # rows no list slot owns are never written here: the FFN reads them as 2 * x_in
         # (features + shortcut, ref quirk R12) through the owner array
         new = torch.empty_like(x_in)
-        _lib.call("mssvt_block_interp_scatter", _i(C), _i(nq), _i(n_upd), _i(interp), _P(attn),
-                  _P(x_in), _P(new), _P(sp.indices), _P(p.win_ind), _P(p.num_wins),
-                  _i(p.cap), _P(p.win_vstart), _P(q_ind), _P(upd_ind), _P(owner), vs3,
+        _lib.call("mssvt_block_interp_scatter", C, nq, n_upd, interp, addr(attn),
+                  addr(x_in), addr(new), addr(sp.indices), addr(p.win_ind), addr(p.num_wins),
+                  p.cap, addr(p.win_vstart), addr(q_ind), addr(upd_ind), addr(owner), vs3,
                   mn3, _lib.stream())
         sp.features = _ffn_tail(block, sp, new, x_in, owner)
     sp.gather_dict = None
@@ -980,8 +969,8 @@ def prepare_group(blocks, sp, p):
                              row_meta=torch.empty((cap_rows, 4), dtype=torch.float32, device=dev),
                              row_src=torch.empty((cap_rows, 2), dtype=torch.int32, device=dev),
                              n_rows=torch.empty(1, dtype=torch.int32, device=dev), row_cap=cap_rows, nq=nq))
-        _lib.call("mssvt_plan_order_multi", _i(len(todo)), _P(p.num_wins), pa([o["nq_valid"] for o in outs]),
-                  ia([o["nq"] for o in outs]), pa([_qmeta(b, p) for b in todo]), _i(p.cap), _i(cap_rows),
+        _lib.call("mssvt_plan_order_multi", len(todo), addr(p.num_wins), pa([o["nq_valid"] for o in outs]),
+                  ia([o["nq"] for o in outs]), pa([_qmeta(b, p) for b in todo]), p.cap, cap_rows,
                   pa([o["perm"] for o in outs]), pa([o["n_act"] for o in outs]), pa([o["q_off"] for o in outs]),
                   pa([o["row_meta"] for o in outs]), pa([o["row_src"] for o in outs]),
                   pa([o["n_rows"] for o in outs]), _lib.stream())
@@ -999,7 +988,7 @@ def prepare_group(blocks, sp, p):
             seen.add(key)
             todo.append((b, key))
     if 1 < len(todo) <= 4:
-        vs3, mn3 = _f3(sp.voxel_size), _f3(sp.point_cloud_range[0:3])
+        vs3, mn3 = _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3])
         # one fill for all tab_row arrays
         rows = mssvt_ops.full_neg1((len(todo), max(N, 1), 4), dev)
         ws = torch.empty((len(todo), max(N, 1), 4), dtype=torch.float32, device=dev)  # written with tab_row
@@ -1009,8 +998,8 @@ def prepare_group(blocks, sp, p):
             upd_ind, n_upd, owner = (p.ind_win1, b.max_num_win1, p.owner_win1) if interp else (q_ind, nq, owner_q)
             nqs.append(nq); nus.append(n_upd); its.append(interp); qis.append(q_ind); uis.append(upd_ind)
             ows.append(owner); zrs.append(_attn_zero_row(p, nq, b.linear1.in_features, dev))
-        _lib.call("mssvt_block_interp_table_multi", _i(len(todo)), ia(nqs), ia(nus), ia(its), _P(sp.indices),
-                  _P(p.win_ind), _P(p.num_wins), _i(p.cap), _P(p.win_vstart), pa(qis), pa(uis),
+        _lib.call("mssvt_block_interp_table_multi", len(todo), ia(nqs), ia(nus), ia(its), addr(sp.indices),
+                  addr(p.win_ind), addr(p.num_wins), p.cap, addr(p.win_vstart), pa(qis), pa(uis),
                   pa(ows), vs3, mn3, ia(zrs), pa([rows[i] for i in range(len(todo))]),
                   pa([ws[i] for i in range(len(todo))]), _lib.stream())
         for i, (b, key) in enumerate(todo):
@@ -1030,11 +1019,11 @@ def _interp_table(block, sp, p, q_ind, nq, upd_ind, n_upd, owner, interp, vs3, m
         N = sp.indices.shape[0]
         tab_row = mssvt_ops.full_neg1((max(N, 1), 4), dev)
         tab_w = torch.empty((max(N, 1), 4), dtype=torch.float32, device=dev)  # written with tab_row
-        _lib.call("mssvt_block_interp_table", _i(nq), _i(n_upd), _i(interp), _P(sp.indices),
-                  _P(p.win_ind), _P(p.num_wins), _i(p.cap), _P(p.win_vstart), _P(q_ind),
-                  _P(upd_ind), _P(owner), vs3, mn3,
-                  _i(_attn_zero_row(p, nq, block.linear1.in_features, dev)), _P(tab_row),
-                  _P(tab_w), _lib.stream())
+        _lib.call("mssvt_block_interp_table", nq, n_upd, interp, addr(sp.indices),
+                  addr(p.win_ind), addr(p.num_wins), p.cap, addr(p.win_vstart), addr(q_ind),
+                  addr(upd_ind), addr(owner), vs3, mn3,
+                  _attn_zero_row(p, nq, block.linear1.in_features, dev), addr(tab_row),
+                  addr(tab_w), _lib.stream())
         tabs[key] = (tab_row, tab_w)
     return tabs[key]
 
@@ -1114,14 +1103,14 @@ def one_scale_plan(block, sp, sync=True):
     p.num_rows = ws[2:3]
     t = block._tables_on(dev)
     occ = st.get("occ") if st.get("sorted") else None
-    _lib.call("mssvt_window_plan_one", *[_i(int(v)) for v in sp.spatial_shape],
-              *[_i(int(v)) for v in block.win1_size], _i(ns), _i(H), _i(t['win1'].shape[0]), _P(t['win1']),
-              _P(p.win_ind), _P(p.num_wins), _i(cap), _P(_voxel_table(sp, st, occ)),
-              _P(st["v_bs_cnt"]), _i(p.with_pad), _i(p.disjoint), _i(N), _P(p.k_ind),
-              _P(p.win_vstart),
-              _P(p.win_cnt), _P(p.pair_base), _P(p.pair_win), _P(p.pair_vox),
-              _P(p.num_rows), _P(occ), _P(st.get("vbase") if occ is not None else None),
-              _P(st.get("level_status") if occ is not None else None), _lib.stream())
+    _lib.call("mssvt_window_plan_one", *[int(v) for v in sp.spatial_shape],
+              *[int(v) for v in block.win1_size], ns, H, t['win1'].shape[0], addr(t['win1']),
+              addr(p.win_ind), addr(p.num_wins), cap, addr(_voxel_table(sp, st, occ)),
+              addr(st["v_bs_cnt"]), p.with_pad, p.disjoint, N, addr(p.k_ind),
+              addr(p.win_vstart),
+              addr(p.win_cnt), addr(p.pair_base), addr(p.pair_win), addr(p.pair_vox),
+              addr(p.num_rows), addr(occ), addr(st.get("vbase") if occ is not None else None),
+              addr(st.get("level_status") if occ is not None else None), _lib.stream())
     p.ws, p.N = ws, N
     if not sync:
         # the window count is final here, ~250 us of GPU work before the block ends: copy it to pinned
@@ -1309,9 +1298,9 @@ def _compress_ws_weights(block, sp):
     ver = tuple(t._version for t in ts) + tuple(t.data_ptr() for t in ts) + _content_key(ts)
     cache = block.__dict__.setdefault("_cmp_ws_cache", {})
     if cache.get("ver") != ver:
-        nbytes = int(_lib.lib().mssvt_compress_ws_packed_bytes(_i(C)))
+        nbytes = int(_lib.lib().mssvt_compress_ws_packed_bytes(C))
         packed = torch.empty((nbytes,), dtype=torch.uint8, device=ts[0].device)
-        _lib.call("mssvt_compress_ws_pack", _i(C), *[_lib.ptr(t.detach().contiguous()) for t in ts], _lib.ptr(packed), _lib.stream())
+        _lib.call("mssvt_compress_ws_pack", C, *[_lib.ptr(t.detach().contiguous()) for t in ts], _lib.ptr(packed), _lib.stream())
         cache["packed"], cache["ver"] = packed, ver
     return cache["packed"]
 
@@ -1329,29 +1318,29 @@ def _compress_forward_fused(block, sp, xhat, x_in):
         return None, p
     N, cap_w, ns = p.N, max(p.N, 1), block.max_num_win1
     ma = block.ms_attn
-    vs3, mn3, ws3 = _f3(sp.voxel_size), _f3(sp.point_cloud_range[0:3]), _f3(p.win_size_m)
+    vs3, mn3, ws3 = _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3]), _lib.f3(p.win_size_m)
     f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)  # noqa: E731
     packed = _compress_ws_weights(block, sp) if CMP_WS and getattr(p, "runs", False) else None
     if packed is not None:
         # a sorted pillar level: every window is a run of consecutive rows -> ONE launch, nothing handed through memory
         new = f32(cap_w, C)
-        _lib.call("mssvt_compress_ws", _i(C), _i(ma.per_head_dim), _f(ma.scale), _i(block.win1_size[2]), _i(ns), _i(N),
-                  _P(p.num_wins), _i(cap_w), _P(sp.indices), _P(p.win_cnt), _P(p.pair_win),
-                  vs3, mn3, ws3, _P(xhat), _P(block.pos_proj[0].weight), _P(block.pos_proj[0].bias),
-                  _P(block.pos_proj[2].bias), _P(ma.to_qs[0].bias), _P(ma.to_kvs[0].bias), _P(ma.projs[0].bias),
-                  _P(packed), _P(new), _lib.stream())
+        _lib.call("mssvt_compress_ws", C, ma.per_head_dim, ma.scale, block.win1_size[2], ns, N,
+                  addr(p.num_wins), cap_w, addr(sp.indices), addr(p.win_cnt), addr(p.pair_win),
+                  vs3, mn3, ws3, addr(xhat), addr(block.pos_proj[0].weight), addr(block.pos_proj[0].bias),
+                  addr(block.pos_proj[2].bias), addr(ma.to_qs[0].bias), addr(ma.to_kvs[0].bias), addr(ma.projs[0].bias),
+                  addr(packed), addr(new), _lib.stream())
         return _compress_fused_tail(block, sp, p, new)
     qp, ktok, score, vp, new = f32(cap_w, C), f32(max(N, 1), C), f32(max(N, 1), C // ma.per_head_dim), \
         f32(max(N, 1), C), f32(cap_w, C)
-    _lib.call("mssvt_compress_fused", _i(C), _i(ma.per_head_dim), _f(ma.scale), _i(ns), _i(N), _P(p.num_wins),
-              _i(cap_w), _P(p.win_ind), _P(sp.indices), _P(p.k_ind), _P(p.win_vstart),
-              _P(p.win_cnt), _P(p.pair_win), vs3, mn3, ws3, _P(xhat),
-              _P(block.pos_proj[0].weight), _P(block.pos_proj[0].bias),
-              _P(block.pos_proj[2].weight), _P(block.pos_proj[2].bias),
-              _P(ma.to_qs[0].weight), _P(ma.to_qs[0].bias), _P(ma.to_kvs[0].weight),
-              _P(ma.to_kvs[0].bias), _P(ma.projs[0].weight), _P(ma.projs[0].bias),
-              _P(qp), _P(ktok), _P(score), _P(vp), _P(new),
-              _i(1 if getattr(block, "ffn_arith", FFN_ARITH) == "f16x3" and _compress_f16_ok(block, sp) else 0), _lib.stream())
+    _lib.call("mssvt_compress_fused", C, ma.per_head_dim, ma.scale, ns, N, addr(p.num_wins),
+              cap_w, addr(p.win_ind), addr(sp.indices), addr(p.k_ind), addr(p.win_vstart),
+              addr(p.win_cnt), addr(p.pair_win), vs3, mn3, ws3, addr(xhat),
+              addr(block.pos_proj[0].weight), addr(block.pos_proj[0].bias),
+              addr(block.pos_proj[2].weight), addr(block.pos_proj[2].bias),
+              addr(ma.to_qs[0].weight), addr(ma.to_qs[0].bias), addr(ma.to_kvs[0].weight),
+              addr(ma.to_kvs[0].bias), addr(ma.projs[0].weight), addr(ma.projs[0].bias),
+              addr(qp), addr(ktok), addr(score), addr(vp), addr(new),
+              1 if getattr(block, "ffn_arith", FFN_ARITH) == "f16x3" and _compress_f16_ok(block, sp) else 0, _lib.stream())
     return _compress_fused_tail(block, sp, p, new)
 
 
@@ -1395,18 +1384,18 @@ def compress_forward(block, sp):
     p = one_scale_plan(block, sp)
     nw, R, ns = p.nw, p.R, block.max_num_win1
     ma = block.ms_attn
-    vs3, mn3, ws3 = _f3(sp.voxel_size), _f3(sp.point_cloud_range[0:3]), _f3(p.win_size_m)
+    vs3, mn3, ws3 = _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3]), _lib.f3(p.win_size_m)
     # key tokens, one row per valid (window, slot) pair: feature + 2-layer positional MLP
     rows = torch.empty((max(R, 1), C), dtype=torch.float32, device=dev)
-    _lib.call("mssvt_compress_pos1", _i(C), _P(p.num_rows), _i(R), _P(p.pair_win),
-              _P(p.pair_vox), _P(sp.indices), _P(p.win_ind), vs3, mn3, ws3,
-              _P(block.pos_proj[0].weight), _P(block.pos_proj[0].bias), _P(rows), _lib.stream())
+    _lib.call("mssvt_compress_pos1", C, addr(p.num_rows), R, addr(p.pair_win),
+              addr(p.pair_vox), addr(sp.indices), addr(p.win_ind), vs3, mn3, ws3,
+              addr(block.pos_proj[0].weight), addr(block.pos_proj[0].bias), addr(rows), _lib.stream())
     k_tok = F.relu(F.linear(rows, block.pos_proj[2].weight.view(C, C), block.pos_proj[2].bias))
-    _lib.call("mssvt_compress_add_features", _i(C), _P(p.num_rows), _i(R), _P(p.pair_vox),
-              _P(xhat), _P(k_tok), _lib.stream())
+    _lib.call("mssvt_compress_add_features", C, addr(p.num_rows), R, addr(p.pair_vox),
+              addr(xhat), addr(k_tok), _lib.stream())
     q_tok = torch.empty((max(nw, 1), C), dtype=torch.float32, device=dev)
-    _lib.call("mssvt_compress_pool", _i(C), _i(ns), _P(p.num_wins), _i(nw), _P(p.k_ind),
-              _P(p.win_vstart), _P(p.win_cnt), _P(xhat), _P(q_tok), _lib.stream())
+    _lib.call("mssvt_compress_pool", C, ns, addr(p.num_wins), nw, addr(p.k_ind),
+              addr(p.win_vstart), addr(p.win_cnt), addr(xhat), addr(q_tok), _lib.stream())
     G = ma.num_head_groups
     nk = ns // G
     pre = torch.empty_like(q_tok)
@@ -1417,10 +1406,10 @@ def compress_forward(block, sp):
         cg = ma.scale_dims[g]
         qp[:, c0:c0 + cg] = ma.to_qs[g](q_tok[:, c0:c0 + cg])
         kv = ma.to_kvs[g](k_tok[:, c0:c0 + cg]).contiguous()  # (R, 2*cg) = [K | V]
-        _lib.call("mssvt_compress_attention_group", _i(C), _i(c0), _i(cg), _i(ma.per_head_dim), _f(ma.scale),
-                  _i(nk), _i(g), _i(p.with_pad), _i(ns), _i(p.N), _P(p.num_wins), _i(nw),
-                  _P(p.win_cnt), _P(p.pair_base), _P(p.k_ind), _P(p.win_vstart),
-                  _P(qp), _P(kv), _P(pre), _lib.stream())
+        _lib.call("mssvt_compress_attention_group", C, c0, cg, ma.per_head_dim, ma.scale,
+                  nk, g, p.with_pad, ns, p.N, addr(p.num_wins), nw,
+                  addr(p.win_cnt), addr(p.pair_base), addr(p.k_ind), addr(p.win_vstart),
+                  addr(qp), addr(kv), addr(pre), _lib.stream())
         c0 += cg
     c0 = 0
     for g in range(G):
@@ -1492,12 +1481,12 @@ def _attention_roofline(net, blk, sp, xhat, event_time_ms, peak_gbs, pmc):
         # csrc/ceiling.hip: k_attn_kvh's bytes through the real work order and key metadata, its instruction counts per
         # window and pass, no dependency between them (the two row-tiled launches either side are not part of it)
         ms_ceil = event_time_ms(lambda: _lib.call(
-            "mssvt_ceiling_attn_kvh", _i(C), _i(0), _i(64), _i(32), _P(xhat), _P(p.kmeta[0]), _P(p.kmeta[1]), _P(od["perm"]),
-            _P(od["n_act"]), _P(od["q_off"]), _P(od["nq_valid"]), _i(od["row_cap"]), _i(p.cap), _P(qbuf), _lib.stream()), 20)
+            "mssvt_ceiling_attn_kvh", C, 0, 64, 32, addr(xhat), addr(p.kmeta[0]), addr(p.kmeta[1]), addr(od["perm"]),
+            addr(od["n_act"]), addr(od["q_off"]), addr(od["nq_valid"]), od["row_cap"], p.cap, addr(qbuf), _lib.stream()), 20)
         # ... and the mix of "Wv applied at the end of the window launch" (round 6: measured instead of argued)
         ms_ceil_wv = event_time_ms(lambda: _lib.call(
-            "mssvt_ceiling_attn_kvh_variant", _i(1), _i(C), _i(0), _i(64), _i(32), _P(xhat), _P(p.kmeta[0]), _P(p.kmeta[1]),
-            _P(od["perm"]), _P(od["n_act"]), _P(od["q_off"]), _P(od["nq_valid"]), _i(od["row_cap"]), _i(p.cap), _P(qbuf),
+            "mssvt_ceiling_attn_kvh_variant", 1, C, 0, 64, 32, addr(xhat), addr(p.kmeta[0]), addr(p.kmeta[1]),
+            addr(od["perm"]), addr(od["n_act"]), addr(od["q_off"]), addr(od["nq_valid"]), od["row_cap"], p.cap, addr(qbuf),
             _lib.stream()), 20)
     nw = int(p.num_wins.item())
     K = blk.key_num_sample
@@ -1575,7 +1564,7 @@ def roofline(net, vc, feats, batch, event_time_ms, peak_gbs, live=None):
                 seen.add(b2.cbs_pattern)
                 attn_lines.append(_attention_roofline(net, b2, sp, xhat, event_time_ms, peak_gbs, counters))
         q_ind, nq, _ = _query(blk, p)
-        vs3, mn3 = _f3(sp.voxel_size), _f3(sp.point_cloud_range[0:3])
+        vs3, mn3 = _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3])
         interp = 1 if blk.use_feature_interpolation else 0
         upd_ind, n_upd, owner = (p.ind_win1, blk.max_num_win1, p.owner_win1) if interp else (q_ind, nq, _query(blk, p)[2])
         tab = _interp_table(blk, sp, p, q_ind, nq, upd_ind, n_upd, owner, interp, vs3, mn3)
@@ -1593,8 +1582,8 @@ def roofline(net, vc, feats, batch, event_time_ms, peak_gbs, live=None):
                 frag = _ffn_f16_weights(_ffn_refs(blk))
                 yc, ync = torch.empty_like(x_in), torch.empty_like(x_in)
                 ms_ceil = event_time_ms(lambda: _lib.call(
-                    "mssvt_ceiling_ffn_ws", _i(x_in.shape[0]), _P(x_in), _P(tab[0]), _P(tab[1]), _P(abuf), _P(frag), _P(yc), _P(ync),
-                    _lib.stream()), 20)
+                    "mssvt_ceiling_ffn_ws", x_in.shape[0], addr(x_in), addr(tab[0]), addr(tab[1]), addr(abuf), addr(frag), addr(yc),
+                    addr(ync), _lib.stream()), 20)
         else:
             ms_ws = None
             ms_up = event_time_ms(lambda: _ffn_tail(blk, sp, None, x_in, None, table=(tab, abuf), phases=1), 20)

@@ -10,13 +10,9 @@
   are read in place through the row stride.
 
 ``boxes_bev_iou_cpu`` (the GT-database sampler's, datasets are out of scope) is not provided."""
-import ctypes
-
 import torch
 
 from . import _lib
-
-_i = ctypes.c_int
 
 
 def nms_gpu(boxes, scores, thresh, pre_maxsize=None, **kwargs):
@@ -82,8 +78,8 @@ def boxes_pairwise(mode, boxes_a, boxes_b, out=None):
     if not (a.device == b.device == out.device) or out.dtype != torch.float32 or tuple(out.shape) != (n, m):
         raise _lib.MssvtHipError("boxes_pairwise: boxes_a, boxes_b and a float32 (N, M) out must share one device")
     if n and m:
-        _lib.call("mssvt_boxes_pairwise", _i(mode), _i(n), ctypes.c_void_p(a.data_ptr()), _i(sa), _i(m),
-                  ctypes.c_void_p(b.data_ptr()), _i(sb), _lib.ptr(out), _lib.stream())
+        _lib.call("mssvt_boxes_pairwise", mode, n, a.data_ptr(), sa, m,
+                  b.data_ptr(), sb, _lib.ptr(out), _lib.stream())
     return out
 
 
@@ -109,9 +105,9 @@ def boxes_iou3d_gpu(boxes_a, boxes_b):
 def _nms_sorted(b, thresh, entry="mssvt_nms_bev"):
     """Indices (into `b`, best first) that greedy NMS keeps among boxes already sorted by descending score."""
     n = int(b.shape[0])
-    ws = torch.empty(int(_lib.lib().mssvt_nms_workspace_bytes(_i(n))) // 8 + 1, dtype=torch.int64, device=b.device)
+    ws = torch.empty(int(_lib.lib().mssvt_nms_workspace_bytes(n)) // 8 + 1, dtype=torch.int64, device=b.device)
     keep = torch.empty(n, dtype=torch.int32, device=b.device)
     cnt = torch.empty(1, dtype=torch.int32, device=b.device)
-    _lib.call(entry, _i(n), _lib.ptr(b), ctypes.c_float(float(thresh)), _lib.ptr(ws), _lib.ptr(keep),
+    _lib.call(entry, n, _lib.ptr(b), float(thresh), _lib.ptr(ws), _lib.ptr(keep),
               _lib.ptr(cnt), _lib.stream())
     return keep[:int(cnt.item())].long()

@@ -25,12 +25,9 @@ ST_DUPLICATE_KEY, ST_TABLE_OVERFLOW, ST_WINDOW_OVERFLOW, ST_UNSORTED = 1, 2, 4, 
 # which costs two host syncs per call; here those checks are opt-in.
 CHECK_COUNTS = False
 
-_i = ctypes.c_int
-
 
 def _ints(xs):
     return [int(v) for v in xs]
-
 
 
 class FillArena(object):
@@ -46,8 +43,8 @@ class FillArena(object):
         dev = torch.device(device)
         if dev.type == "cuda":
             whole = torch.empty(numel + zero_numel, dtype=torch.int32, device=dev)
-            _lib.call("mssvt_fill_two", _lib.ptr_fast(whole), ctypes.c_longlong(numel), _i(-1),
-                      ctypes.c_void_p(whole.data_ptr() + 4 * numel), ctypes.c_longlong(zero_numel), _i(0), _lib.stream())
+            _lib.call("mssvt_fill_two", _lib.addr(whole), numel, -1,
+                      whole.data_ptr() + 4 * numel, zero_numel, 0, _lib.stream())
             self.buf, self.zeros = whole[:numel], whole[numel:]
         else:
             self.buf = torch.full((numel,), -1, dtype=torch.int32, device=dev)
@@ -89,7 +86,7 @@ def full_neg1(shape, device):
 
 
 def hash_workspace(num_voxels, batch_size, device):
-    n = int(_lib.lib().mssvt_hash_workspace_ints(_i(int(num_voxels)), _i(int(batch_size))))
+    n = int(_lib.lib().mssvt_hash_workspace_ints(int(num_voxels), int(batch_size)))
     return torch.empty(n, dtype=torch.int32, device=device)
 
 
@@ -109,8 +106,8 @@ def build_hash_table(batch_size, hash_size, spatial_shape, voxel_indices, v_bs_c
     n = voxel_indices.shape[0]
     table = full_neg1((batch_size, hash_size, 2), voxel_indices.device)
     ws = workspace if workspace is not None else hash_workspace(n, batch_size, voxel_indices.device)
-    _lib.call("mssvt_build_mapping_with_hash", _i(x_max), _i(y_max), _i(z_max), _i(n),
-              _i(int(hash_size)), _i(int(batch_size)), _lib.ptr(voxel_indices), _lib.ptr(v_bs_cnt),
+    _lib.call("mssvt_build_mapping_with_hash", x_max, y_max, z_max, n,
+              int(hash_size), int(batch_size), _lib.ptr(voxel_indices), _lib.ptr(v_bs_cnt),
               _lib.ptr(table), _lib.ptr(ws), _lib.stream())
     build_hash_table.last_status = ws[0:1]  # device word: ST_* bits (read lazily by the fused path)
     return table
@@ -133,8 +130,8 @@ def window_partition_device(win_size, max_num_wins, batch_size, hash_size, spati
     win = torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev)
     vcount = torch.empty(batch_size, dtype=torch.int32, device=dev)  # every entry is written by the scan kernel
     ws = workspace if workspace is not None else hash_workspace(n, batch_size, dev)
-    _lib.call("mssvt_window_partition_compact", _i(x_wgs), _i(y_wgs), _i(z_wgs), _i(x_ws), _i(y_ws),
-              _i(z_ws), _i(n), _i(int(max_num_wins)), _i(int(hash_size)), _i(int(batch_size)),
+    _lib.call("mssvt_window_partition_compact", x_wgs, y_wgs, z_wgs, x_ws, y_ws,
+              z_ws, n, int(max_num_wins), int(hash_size), int(batch_size),
               _lib.ptr(voxel_indices), _lib.ptr(win), _lib.ptr(table), _lib.ptr(vcount), _lib.ptr(ws),
               _lib.stream())
     return win, table, vcount, ws
@@ -151,14 +148,14 @@ def window_partitions_device(win_sizes, max_num_wins, batch_size, hash_size, spa
     scratch = [full_neg1((batch_size, hash_size, 2), dev) for _ in range(k)]
     wins = [torch.empty((max(n, 1), 4), dtype=torch.int32, device=dev) for _ in range(k)]
     vcounts = torch.empty((k, batch_size), dtype=torch.int32, device=dev)
-    stride = int(_lib.lib().mssvt_hash_workspace_ints(_i(int(n)), _i(int(batch_size))))
+    stride = int(_lib.lib().mssvt_hash_workspace_ints(int(n), int(batch_size)))
     ws = torch.empty((k, stride), dtype=torch.int32, device=dev)
     ints = lambda rows: (ctypes.c_int * (3 * k))(*[int(v) for r in rows for v in r])  # noqa: E731
     ptrs = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])  # noqa: E731
-    _lib.call("mssvt_window_partition_multi", _i(k), ints(spatial_shapes), ints(win_sizes),
-              (ctypes.c_int * k)(*[int(m) for m in max_num_wins]), _i(n), _i(int(hash_size)), _i(int(batch_size)),
+    _lib.call("mssvt_window_partition_multi", k, ints(spatial_shapes), ints(win_sizes),
+              (ctypes.c_int * k)(*[int(m) for m in max_num_wins]), n, int(hash_size), int(batch_size),
               _lib.ptr(voxel_indices), ptrs(wins), ptrs(tables), ptrs(scratch), ptrs([vcounts[i] for i in range(k)]),
-              _lib.ptr(ws), ctypes.c_longlong(stride), _lib.stream())
+              _lib.ptr(ws), stride, _lib.stream())
     return [(wins[i], tables[i], vcounts[i], ws[i]) for i in range(k)]
 
 
@@ -198,9 +195,9 @@ def gather_two_window_voxels(spatial_shape, win_size, max_num_odd, max_num_even,
     maxes = _ints((max_num_odd, max_num_even, max_num_win1, max_num_win2))
     inds = [torch.full((nw, m), -1, dtype=torch.int32, device=dev) for m in maxes]
     coords = [torch.zeros((nw, m, 3), dtype=torch.int32, device=dev) for m in maxes]
-    _lib.call("mssvt_gather_two_window_voxels_with_hash", _i(x_max), _i(y_max), _i(z_max), _i(x_ws),
-              _i(y_ws), _i(z_ws), *[_i(m) for m in maxes], _i(nw), _i(int(hash_size)),
-              *[_i(t.shape[0]) for t in tabs], *[_lib.ptr(t) for t in inds],
+    _lib.call("mssvt_gather_two_window_voxels_with_hash", x_max, y_max, z_max, x_ws,
+              y_ws, z_ws, *maxes, nw, int(hash_size),
+              *[t.shape[0] for t in tabs], *[_lib.ptr(t) for t in inds],
               *[_lib.ptr(t) for t in coords], *[_lib.ptr(t) for t in tabs], _lib.ptr(win_indices),
               _lib.ptr(dense_map), _lib.stream())
     return (*inds, *coords)
@@ -220,8 +217,8 @@ def gather_one_window_voxels(spatial_shape, win_size, max_num_win1, vox_query_wi
     tab = vox_query_win1.to(device=dev, dtype=torch.int32).contiguous()
     ind = torch.full((nw, int(max_num_win1)), -1, dtype=torch.int32, device=dev)
     coord = torch.zeros((nw, int(max_num_win1), 3), dtype=torch.int32, device=dev)
-    _lib.call("mssvt_gather_one_window_voxels_with_hash", _i(x_max), _i(y_max), _i(z_max), _i(x_ws),
-              _i(y_ws), _i(z_ws), _i(int(max_num_win1)), _i(nw), _i(int(hash_size)), _i(tab.shape[0]),
+    _lib.call("mssvt_gather_one_window_voxels_with_hash", x_max, y_max, z_max, x_ws,
+              y_ws, z_ws, int(max_num_win1), nw, int(hash_size), tab.shape[0],
               _lib.ptr(ind), _lib.ptr(coord), _lib.ptr(tab), _lib.ptr(win_indices), _lib.ptr(dense_map),
               _lib.stream())
     return ind, coord
@@ -246,7 +243,7 @@ class _GroupFeatures(torch.autograd.Function):
             assert N == int(features_batch_cnt.sum()), (features.shape, features_batch_cnt)
             assert M == int(idx_batch_cnt.sum()), (idx.shape, idx_batch_cnt)
         out = torch.zeros((M, C, nsample), dtype=torch.float32, device=features.device)
-        _lib.call("mssvt_group_features", _i(B), _i(M), _i(C), _i(nsample), _lib.ptr(features),
+        _lib.call("mssvt_group_features", B, M, C, nsample, _lib.ptr(features),
                   _lib.ptr(features_batch_cnt), _lib.ptr(idx), _lib.ptr(idx_batch_cnt), _lib.ptr(out),
                   _lib.stream())
         ctx.for_backwards = (B, N, idx, features_batch_cnt, idx_batch_cnt)
@@ -258,7 +255,7 @@ class _GroupFeatures(torch.autograd.Function):
         M, C, nsample = grad_out.shape
         grad_out = grad_out.contiguous()
         grad = torch.zeros((N, C), dtype=torch.float32, device=grad_out.device)
-        _lib.call("mssvt_group_features_grad", _i(B), _i(M), _i(C), _i(N), _i(nsample),
+        _lib.call("mssvt_group_features_grad", B, M, C, N, nsample,
                   _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(idx_batch_cnt),
                   _lib.ptr(features_batch_cnt), _lib.ptr(grad), _lib.stream())
         return grad, None, None, None

@@ -11,8 +11,6 @@ names, constructor arguments, attributes and state-dict keys
 the GPU: rocBLAS batched GEMMs); the module fast path runs the same arithmetic in
 the fused HIP window kernel (``mssvt_amd/fused.py``) straight from the weights.
 """
-import ctypes
-
 import torch
 from torch import nn
 
@@ -37,8 +35,8 @@ def batch_counts(indices, batch_size):
             and indices.shape[1] == 4:
         from . import _lib
         out = torch.empty(batch_size, dtype=torch.int32, device=indices.device)
-        _lib.call("mssvt_batch_counts", _lib.ptr(indices), ctypes.c_int(indices.shape[0]),
-                  ctypes.c_int(int(batch_size)), _lib.ptr(out), _lib.stream())
+        _lib.call("mssvt_batch_counts", _lib.ptr(indices), indices.shape[0],
+                  int(batch_size), _lib.ptr(out), _lib.stream())
         return out
     return torch.bincount(indices[:, 0].long(), minlength=batch_size)[:batch_size].to(torch.int32)
 
@@ -99,14 +97,13 @@ class SparseTensor(object):
                 and self.map_table is not None and self.indices.dtype == torch.int32):
             # one gather pass through the hash table instead of zero fill + scatter + permute copy
             from . import _lib
-            ci = ctypes.c_int
             X, Y, Z = (int(v) for v in self.spatial_shape)
             out = torch.empty([self.batch_size, f.shape[1]] + zyx, dtype=torch.float32, device=f.device)
             cnt = getattr(self, "v_bs_cnt", None)
             if cnt is None or getattr(self, "_cnt_of", None) is not self.indices:
                 cnt = batch_counts(self.indices.contiguous(), self.batch_size)
-            _lib.call("mssvt_dense_bev", _lib.ptr(f.contiguous()), ci(f.shape[1]), _lib.ptr(self.map_table),
-                      ci(int(self.hash_size)), _lib.ptr(cnt), ci(int(self.batch_size)), ci(X), ci(Y), ci(Z),
+            _lib.call("mssvt_dense_bev", _lib.ptr(f.contiguous()), f.shape[1], _lib.ptr(self.map_table),
+                      int(self.hash_size), _lib.ptr(cnt), int(self.batch_size), X, Y, Z,
                       _lib.ptr(out), _lib.stream())
             return out
         res = scatter_nd(self.indices.to(self.features.device).long(), self.features, shape)

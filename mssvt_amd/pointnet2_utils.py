@@ -5,13 +5,9 @@ Same names and signatures as the reference's
 (``farthest_point_sample`` :36, ``gather_operation`` :73, ``three_nn`` :105,
 ``grouping_operation`` :197).  Backed by libmssvt_hip.so; no CPU fallback.
 """
-import ctypes
-
 import torch
 
 from . import _lib
-
-_i = ctypes.c_int
 
 
 def farthest_point_sample(xyz, npoint):
@@ -23,7 +19,7 @@ def farthest_point_sample(xyz, npoint):
     B, N, _ = xyz.shape
     out = torch.empty((B, npoint), dtype=torch.int32, device=xyz.device)
     temp = torch.full((B, N), 1e10, dtype=torch.float32, device=xyz.device)
-    _lib.call("mssvt_farthest_point_sampling", _i(B), _i(N), _i(int(npoint)), _lib.ptr(xyz),
+    _lib.call("mssvt_farthest_point_sampling", B, N, int(npoint), _lib.ptr(xyz),
               _lib.ptr(temp), _lib.ptr(out), _lib.stream())
     return out
 
@@ -40,7 +36,7 @@ class _GatherPoints(torch.autograd.Function):
         B, npoint = idx.shape
         _, C, N = features.shape
         out = torch.empty((B, C, npoint), dtype=torch.float32, device=features.device)
-        _lib.call("mssvt_gather_points", _i(B), _i(C), _i(N), _i(npoint), _lib.ptr(features),
+        _lib.call("mssvt_gather_points", B, C, N, npoint, _lib.ptr(features),
                   _lib.ptr(idx), _lib.ptr(out), _lib.stream())
         ctx.for_backwards = (idx, C, N)
         return out
@@ -51,7 +47,7 @@ class _GatherPoints(torch.autograd.Function):
         B, npoint = idx.shape
         grad = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
         grad_out = grad_out.contiguous()
-        _lib.call("mssvt_gather_points_grad", _i(B), _i(C), _i(N), _i(npoint), _lib.ptr(grad_out),
+        _lib.call("mssvt_gather_points_grad", B, C, N, npoint, _lib.ptr(grad_out),
                   _lib.ptr(idx), _lib.ptr(grad), _lib.stream())
         return grad, None
 
@@ -69,7 +65,7 @@ def three_nn(unknown, known):
     m = known.shape[1]
     dist2 = torch.empty((B, N, 3), dtype=torch.float32, device=unknown.device)
     idx = torch.empty((B, N, 3), dtype=torch.int32, device=unknown.device)
-    _lib.call("mssvt_three_nn", _i(B), _i(N), _i(m), _lib.ptr(unknown), _lib.ptr(known),
+    _lib.call("mssvt_three_nn", B, N, m, _lib.ptr(unknown), _lib.ptr(known),
               _lib.ptr(dist2), _lib.ptr(idx), _lib.stream())
     return torch.sqrt(dist2), idx
 
@@ -83,7 +79,7 @@ class _GroupPoints(torch.autograd.Function):
         B, npts, nsample = idx.shape
         _, C, N = features.shape
         out = torch.empty((B, C, npts, nsample), dtype=torch.float32, device=features.device)
-        _lib.call("mssvt_group_points", _i(B), _i(C), _i(N), _i(npts), _i(nsample),
+        _lib.call("mssvt_group_points", B, C, N, npts, nsample,
                   _lib.ptr(features), _lib.ptr(idx), _lib.ptr(out), _lib.stream())
         ctx.for_backwards = (idx, N)
         return out
@@ -94,7 +90,7 @@ class _GroupPoints(torch.autograd.Function):
         B, C, npts, nsample = grad_out.shape
         grad = torch.zeros((B, C, N), dtype=torch.float32, device=grad_out.device)
         grad_out = grad_out.contiguous()
-        _lib.call("mssvt_group_points_grad", _i(B), _i(C), _i(N), _i(npts), _i(nsample),
+        _lib.call("mssvt_group_points_grad", B, C, N, npts, nsample,
                   _lib.ptr(grad_out), _lib.ptr(idx), _lib.ptr(grad), _lib.stream())
         return grad, None
 

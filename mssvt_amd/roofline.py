@@ -4,13 +4,9 @@
 inputs, times it with HIP events on the launching stream, and divides the kernel's
 ALGORITHMIC bytes (computed from the actual input, not hard-coded) by that time.
 """
-import ctypes
-
 import torch
 
 from . import _lib, mssvt_ops
-
-_i = ctypes.c_int
 
 
 def _gather_two_window(net, vc, batch, event_time_ms, peak_gbs):
@@ -32,9 +28,9 @@ def _gather_two_window(net, vc, batch, event_time_ms, peak_gbs):
     tabs = [t['odd'], t['even'], t['win1'], t['win2']]
 
     def launch():
-        _lib.call("mssvt_gather_two_window_voxels_with_hash", *[_i(v) for v in sp_shape],
-                  *[_i(v) for v in blk.win1_size], *[_i(m) for m in maxes], _i(nw), _i(net.hash_size),
-                  *[_i(x.shape[0]) for x in tabs], *[_lib.ptr(x) for x in inds], *[_lib.ptr(x) for x in coords],
+        _lib.call("mssvt_gather_two_window_voxels_with_hash", *sp_shape,
+                  *blk.win1_size, *maxes, nw, net.hash_size,
+                  *[x.shape[0] for x in tabs], *[_lib.ptr(x) for x in inds], *[_lib.ptr(x) for x in coords],
                   *[_lib.ptr(x) for x in tabs], _lib.ptr(win), _lib.ptr(table), _lib.stream())
 
     ms = event_time_ms(launch, 20)

@@ -24,7 +24,6 @@ import torch.nn.functional as F
 
 from . import _lib, fused, mssvt_ops
 
-_i = ctypes.c_int
 
 
 # ---------------------------------------------------------------------------------------------------------
@@ -39,7 +38,7 @@ def _ranges_sum(src, start, end, idx, w, n_dst):
     C = src.shape[1]
     dst = torch.empty((n_dst, C), dtype=torch.float32, device=src.device)
     if n_dst:
-        _lib.call("mssvt_segment_sum_rows_ranges", _i(C), _i(n_dst), _lib.ptr(start), _lib.ptr(end), _lib.ptr(idx),
+        _lib.call("mssvt_segment_sum_rows_ranges", C, n_dst, _lib.ptr(start), _lib.ptr(end), _lib.ptr(idx),
                   _lib.ptr(w), _lib.ptr(src), _lib.ptr(dst), _lib.stream())
     return dst
 
@@ -126,9 +125,9 @@ def _sum_into(seg, src, dst, c0, accumulate):
     if seg.pending is not None:
         seg._cut(int(seg.pending.item()))
     src = src.contiguous()
-    _lib.call("mssvt_segment_sum_rows_strided", _i(cg), _i(seg.n_dst), _lib.ptr(seg.start), _lib.ptr(seg.end), _lib.ptr(seg.idx),
-              _lib.ptr(seg.w), _lib.ptr(src), _i(cg), ctypes.c_void_p(view.data_ptr()), _i(dst.stride(0)),
-              _i(1 if accumulate else 0), _lib.stream())
+    _lib.call("mssvt_segment_sum_rows_strided", cg, seg.n_dst, _lib.ptr(seg.start), _lib.ptr(seg.end), _lib.ptr(seg.idx),
+              _lib.ptr(seg.w), _lib.ptr(src), cg, view.data_ptr(), dst.stride(0),
+              1 if accumulate else 0, _lib.stream())
     h = seg.heavy
     if h is not None:  # the long lists (empty ranges above: 0 written / added), chunk sums added in chunk order
         part = _ranges_sum(src, h["c_start"], h["c_end"], seg.idx, seg.w, h["n_chunks"])
@@ -176,7 +175,7 @@ _csr_ws = {}
 
 
 def _csr_workspace(dev, nnz, n_src):
-    need = int(_lib.lib().mssvt_csr_transpose_workspace_bytes(_i(nnz), _i(n_src)))
+    need = int(_lib.lib().mssvt_csr_transpose_workspace_bytes(nnz, n_src))
     ws = _csr_ws.get(dev)
     if ws is None or ws.numel() < need:
         ws = _csr_ws[dev] = torch.empty((need,), dtype=torch.uint8, device=dev)
@@ -201,8 +200,8 @@ class Csr(object):
         t_idx = torch.empty(nnz, dtype=torch.int32, device=dev)
         t_w = None if w is None else torch.empty(nnz, dtype=torch.float32, device=dev)
         longest = torch.empty(1, dtype=torch.int32, device=dev)
-        _lib.call("mssvt_csr_transpose", _i(nnz), _i(self.n_dst), _i(self.n_src), _lib.ptr(off), _lib.ptr(idx) if nnz else None,
-                  _lib.ptr(w) if nnz else None, _i(-1 if drop_src is None else int(drop_src)), _i(CHUNK), _lib.ptr(t_off),
+        _lib.call("mssvt_csr_transpose", nnz, self.n_dst, self.n_src, _lib.ptr(off), _lib.ptr(idx) if nnz else None,
+                  _lib.ptr(w) if nnz else None, -1 if drop_src is None else int(drop_src), CHUNK, _lib.ptr(t_off),
                   _lib.ptr(t_idx) if nnz else None, _lib.ptr(t_w) if (nnz and w is not None) else None, _lib.ptr(longest),
                   _lib.ptr(_csr_workspace(dev, nnz, self.n_src)) if nnz else None, _lib.stream())
         if off is None:
@@ -232,7 +231,7 @@ def _gather_unique(idx, n_src):
     inv = torch.empty(c.n_src, dtype=torch.int32, device=dev)
     bwd_idx = torch.empty(c.n_src, dtype=torch.int32, device=dev)
     bwd_end = torch.empty(c.n_src, dtype=torch.int32, device=dev)
-    _lib.call("mssvt_train_unique_inverse", _i(nnz), _i(c.n_src), _lib.ptr(idx) if nnz else None, _lib.ptr(inv), _lib.ptr(bwd_idx),
+    _lib.call("mssvt_train_unique_inverse", nnz, c.n_src, _lib.ptr(idx) if nnz else None, _lib.ptr(inv), _lib.ptr(bwd_idx),
               _lib.ptr(bwd_end), _lib.stream())
     c.off = torch.arange(nnz + 1, dtype=torch.int32, device=dev)
     c.idx, c.w = idx, None
@@ -289,7 +288,7 @@ class _PairAttention(torch.autograd.Function):
         lse = torch.empty((R, heads), dtype=torch.float32, device=q.device)
         nw = wins["q_off"].numel()
         if R > 0:
-            _lib.call("mssvt_pair_attention_fwd", _i(nw), _i(cg), _i(heads), _i(hd), _lib.ptr(wins["q_off"]),
+            _lib.call("mssvt_pair_attention_fwd", nw, cg, heads, hd, _lib.ptr(wins["q_off"]),
                       _lib.ptr(wins["q_cnt"]), _lib.ptr(wins["k_off"]), _lib.ptr(wins["k_cnt"]), _lib.ptr(q), _lib.ptr(kv),
                       _lib.ptr(O), _lib.ptr(lse), _lib.stream())
         ctx.save_for_backward(q, kv, O, lse)
@@ -303,7 +302,7 @@ class _PairAttention(torch.autograd.Function):
         wins = ctx.wins
         dq, dkv = torch.empty_like(q), torch.empty_like(kv)
         if kv.shape[0] > 0 and nw > 0:
-            _lib.call("mssvt_pair_attention_bwd", _i(nw), _i(cg), _i(heads), _i(hd), _lib.ptr(wins["q_off"]),
+            _lib.call("mssvt_pair_attention_bwd", nw, cg, heads, hd, _lib.ptr(wins["q_off"]),
                       _lib.ptr(wins["q_cnt"]), _lib.ptr(wins["k_off"]), _lib.ptr(wins["k_cnt"]), _lib.ptr(q), _lib.ptr(kv),
                       _lib.ptr(O), _lib.ptr(lse), _lib.ptr(dO.contiguous()), _lib.ptr(dq) if q.shape[0] else None,
                       _lib.ptr(dkv), _lib.stream())
@@ -326,7 +325,7 @@ _wgrad_ws = {}
 
 
 def _wgrad_workspace(dev, M, cin, cout):
-    need = int(_lib.lib().mssvt_linear_wgrad_workspace_floats(_i(M), _i(cin), _i(cout)))
+    need = int(_lib.lib().mssvt_linear_wgrad_workspace_floats(M, cin, cout))
     ws = _wgrad_ws.get(dev)
     if ws is None or ws.numel() < need:
         ws = _wgrad_ws[dev] = torch.empty((need,), dtype=torch.float32, device=dev)
@@ -350,8 +349,8 @@ def _linear_rows(x, w, transpose_w, b, relu, n_out, scale=1.0, split16=False):
     M, K = x.shape
     y = torch.empty((M, n_out), dtype=torch.float32, device=x.device)
     if M:
-        _lib.call("mssvt_linear_rows_h" if split16 else "mssvt_linear_rows", _i(M), _i(K), _i(n_out), _lib.ptr(x), _i(K), _lib.ptr(w),
-                  _i(1 if transpose_w else 0), _lib.ptr(b), _i(1 if relu else 0), ctypes.c_float(scale), _lib.ptr(y), _i(n_out),
+        _lib.call("mssvt_linear_rows_h" if split16 else "mssvt_linear_rows", M, K, n_out, _lib.ptr(x), K, _lib.ptr(w),
+                  1 if transpose_w else 0, _lib.ptr(b), 1 if relu else 0, scale, _lib.ptr(y), n_out,
                   _lib.stream())
     return y
 
@@ -404,7 +403,7 @@ class _Linear(torch.autograd.Function):
             dw = alloc(w.shape, dtype=w.dtype, device=w.device)
             db = alloc((cout,), dtype=w.dtype, device=w.device) if ctx.has_bias else None
             if M > 0:
-                _lib.call("mssvt_linear_wgrad", _i(M), _i(cin), _i(cout), _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw),
+                _lib.call("mssvt_linear_wgrad", M, cin, cout, _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dw),
                           _lib.ptr(db), _lib.ptr(_wgrad_workspace(x.device, M, cin, cout)), _lib.stream())
                 if sc != 1.0:  # (cout x cin and cout elements: two small launches instead of two over the rows)
                     dw.mul_(sc)
@@ -436,8 +435,8 @@ class _LayerNorm(torch.autograd.Function):
     def forward(ctx, x, w, b, eps):
         x = x.contiguous()
         y = torch.empty_like(x)
-        _lib.call("mssvt_layer_norm", _lib.ptr(x), _i(x.shape[0]), _i(x.shape[1]), _lib.ptr(w), _lib.ptr(b),
-                  ctypes.c_float(eps), _lib.ptr(y), _lib.stream())
+        _lib.call("mssvt_layer_norm", _lib.ptr(x), x.shape[0], x.shape[1], _lib.ptr(w), _lib.ptr(b),
+                  eps, _lib.ptr(y), _lib.stream())
         ctx.save_for_backward(x, w)
         ctx.eps = eps
         return x.view_as(x), y
@@ -454,8 +453,8 @@ class _LayerNorm(torch.autograd.Function):
         ws = _wgrad_ws.get(("ln", x.device))
         if ws is None:
             ws = _wgrad_ws[("ln", x.device)] = torch.empty((512 * 2 * 256,), dtype=torch.float32, device=x.device)
-        _lib.call("mssvt_layer_norm_backward_residual", _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dres), _i(N), _i(C), _lib.ptr(w),
-                  ctypes.c_float(ctx.eps), _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), _lib.stream())
+        _lib.call("mssvt_layer_norm_backward_residual", _lib.ptr(x), _lib.ptr(dy), _lib.ptr(dres), N, C, _lib.ptr(w),
+                  ctx.eps, _lib.ptr(dx), _lib.ptr(dw), _lib.ptr(db), _lib.ptr(ws), _lib.stream())
         return dx, dw, db, None
 
 
@@ -525,7 +524,7 @@ class _Tokens(torch.autograd.Function):
             M, c0, cg = pt["rows"].numel(), pt["c0"], pt["c1"] - pt["c0"]
             tok = torch.empty((M, cg), dtype=torch.float32, device=xhat.device)
             if M:
-                _lib.call("mssvt_train_tok_forward", _i(M), _i(C), _i(c0), _i(cg), _lib.ptr(pt["rows"]), _lib.ptr(xhat),
+                _lib.call("mssvt_train_tok_forward", M, C, c0, cg, _lib.ptr(pt["rows"]), _lib.ptr(xhat),
                           _lib.ptr(pt["geo"]), _lib.ptr(w), _lib.ptr(b), _lib.ptr(tok), _lib.stream())
             outs.append(tok)
         ctx.save_for_backward(w, b)
@@ -554,7 +553,7 @@ class _Tokens(torch.autograd.Function):
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             n = len(parts)
             Ms = [pt["rows"].numel() for pt in parts]
-            sizes = [int(_lib.lib().mssvt_train_tok_slab_floats(_i(M), _i(pt["c1"] - pt["c0"]))) for M, pt in zip(Ms, parts)]
+            sizes = [int(_lib.lib().mssvt_train_tok_slab_floats(M, pt["c1"] - pt["c0"])) for M, pt in zip(Ms, parts)]
             slab = torch.empty((max(1, sum(sizes)),), dtype=torch.float32, device=dev)
             addr, at = [], 0
             for pt, g, M, sz in zip(parts, grads, Ms, sizes):
@@ -562,12 +561,12 @@ class _Tokens(torch.autograd.Function):
                 addr.append(a)
                 at += sz
                 if M:
-                    _lib.call("mssvt_train_tok_backward_partial", _i(M), _i(pt["c0"]), _i(pt["c1"] - pt["c0"]), _lib.ptr(pt["geo"]),
-                              _lib.ptr(w), _lib.ptr(b), _lib.ptr(g), ctypes.c_void_p(a), _lib.stream())
+                    _lib.call("mssvt_train_tok_backward_partial", M, pt["c0"], pt["c1"] - pt["c0"], _lib.ptr(pt["geo"]),
+                              _lib.ptr(w), _lib.ptr(b), _lib.ptr(g), a, _lib.stream())
             dw = torch.empty((C, 6), dtype=torch.float32, device=dev)
             db = torch.empty((C,), dtype=torch.float32, device=dev)
             arr = ctypes.c_int * n
-            _lib.call("mssvt_train_tok_backward_reduce", _i(C), _i(n), arr(*Ms), arr(*[pt["c0"] for pt in parts]),
+            _lib.call("mssvt_train_tok_backward_reduce", C, n, arr(*Ms), arr(*[pt["c0"] for pt in parts]),
                       arr(*[pt["c1"] - pt["c0"] for pt in parts]), (ctypes.c_void_p * n)(*addr), _lib.ptr(dw), _lib.ptr(db),
                       _lib.stream())
             dw = dw.reshape(ctx.wshape)
@@ -628,8 +627,8 @@ def _plan_index_sets(block, sp, p):
         totals = torch.zeros(2, dtype=torch.int32, device=dev)
         cnts = [torch.empty(p.cap, dtype=torch.int32, device=dev) for _ in range(2)]
         for g in range(2):
-            _lib.call("mssvt_train_key_counts", _i(p.cap), _i(kdim[g]), _lib.ptr(p.num_wins), _lib.ptr(p.kmeta[g]), _lib.ptr(cnts[g]),
-                      ctypes.c_void_p(totals.data_ptr() + 4 * g), _lib.stream())
+            _lib.call("mssvt_train_key_counts", p.cap, kdim[g], _lib.ptr(p.num_wins), _lib.ptr(p.kmeta[g]), _lib.ptr(cnts[g]),
+                      totals.data_ptr() + 4 * g, _lib.stream())
         words = [p.num_wins.reshape(1), totals]
     else:
         in_use = torch.arange(p.cap, device=dev).unsqueeze(1) < p.num_wins
@@ -656,7 +655,7 @@ def _plan_index_sets(block, sp, p):
             k_win = torch.empty(Kg, dtype=torch.int32, device=dev)
             k_geo = torch.empty((Kg, 8), dtype=torch.float32, device=dev)
             if nw and Kg:
-                _lib.call("mssvt_train_key_compact", _i(nw), _i(K), _lib.ptr(km), _lib.ptr(p.wcentre), _lib.ptr(koff),
+                _lib.call("mssvt_train_key_compact", nw, K, _lib.ptr(km), _lib.ptr(p.wcentre), _lib.ptr(koff),
                           _lib.ptr(k_rows), _lib.ptr(k_win), _lib.ptr(k_geo), _lib.stream())
             keys.append(dict(k_rows=k_rows, k_win=k_win, k_geo=k_geo, k_csr=Csr.gather(k_rows, N), k_off=koff,
                              k_cnt=nk.contiguous()))
@@ -694,7 +693,7 @@ def _block_index_sets(block, sp, p):
         q_rows = torch.empty(R, dtype=torch.int32, device=dev)
         q_geo = torch.empty((R, 8), dtype=torch.float32, device=dev)
         if R:
-            _lib.call("mssvt_train_query_sets", _i(R), _lib.ptr(od["row_meta"]), _lib.ptr(od["row_src"]), _lib.ptr(p.wcentre),
+            _lib.call("mssvt_train_query_sets", R, _lib.ptr(od["row_meta"]), _lib.ptr(od["row_src"]), _lib.ptr(p.wcentre),
                       _lib.ptr(q_rows), _lib.ptr(q_geo), _lib.stream())
         qs = {"q_rows": q_rows, "q_geo": q_geo, "q_rel": q_geo[:, :3], "q_centre": q_geo[:, 3:6]}
         # (a voxel is on one window's query list when every window size is odd, ref mssvt_backbone.py:94-97, AND no
@@ -713,17 +712,17 @@ def _block_index_sets(block, sp, p):
     zero_row = p.cap * nq  # a virtual row of the (never allocated) padded attention buffer
     tab_row = torch.full((max(N, 1), 4), -1, dtype=torch.int32, device=dev)
     tab_w = torch.zeros((max(N, 1), 4), dtype=torch.float32, device=dev)
-    _lib.call("mssvt_block_interp_table", _i(nq), _i(n_upd), _i(interp), _lib.ptr(sp.indices), _lib.ptr(p.win_ind),
-              _lib.ptr(p.num_wins), _i(p.cap), _lib.ptr(p.win_vstart), _lib.ptr(q_ind), _lib.ptr(upd_ind),
-              _lib.ptr(owner), fused._f3(sp.voxel_size), fused._f3(sp.point_cloud_range[0:3]), _i(zero_row),
+    _lib.call("mssvt_block_interp_table", nq, n_upd, interp, _lib.ptr(sp.indices), _lib.ptr(p.win_ind),
+              _lib.ptr(p.num_wins), p.cap, _lib.ptr(p.win_vstart), _lib.ptr(q_ind), _lib.ptr(upd_ind),
+              _lib.ptr(owner), _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3]), zero_row,
               _lib.ptr(tab_row), _lib.ptr(tab_w), _lib.stream())
     inv = torch.full((zero_row + 1,), R, dtype=torch.int32, device=dev)  # padded attention row -> compact row
     inv[od["row_src"][:R, 1].long()] = torch.arange(R, dtype=torch.int32, device=dev)
     owned = torch.empty(N, dtype=torch.bool, device=dev)
     idx3 = torch.empty(3 * N, dtype=torch.int32, device=dev)
     w3 = torch.empty(3 * N, dtype=torch.float32, device=dev)
-    _lib.call("mssvt_train_interp_compact", _i(N), _i(R), _lib.ptr(inv), _lib.ptr(tab_row), _lib.ptr(tab_w), _lib.ptr(idx3),
-              _lib.ptr(w3), ctypes.c_void_p(owned.data_ptr()), _lib.stream())
+    _lib.call("mssvt_train_interp_compact", N, R, _lib.ptr(inv), _lib.ptr(tab_row), _lib.ptr(tab_w), _lib.ptr(idx3),
+              _lib.ptr(w3), owned.data_ptr(), _lib.stream())
     off3 = torch.arange(0, 3 * N + 1, 3, dtype=torch.int32, device=dev)
     s["interp_csr"] = Csr(off3, idx3, w3, R + 1, drop_src=R, fwd_longest=3)
     s["owned"] = owned
@@ -749,7 +748,7 @@ class _BlockTail(torch.autograd.Function):
         N, C = x_in.shape
         new = torch.empty_like(x_in)
         f = csr.fwd
-        _lib.call("mssvt_segment_sum_rows_residual", _i(C), _i(N), _lib.ptr(f.start), _lib.ptr(f.end), _lib.ptr(f.idx),
+        _lib.call("mssvt_segment_sum_rows_residual", C, N, _lib.ptr(f.start), _lib.ptr(f.end), _lib.ptr(f.idx),
                   _lib.ptr(f.w), _lib.ptr(attn_ext), _lib.ptr(x_in), _lib.ptr(row_a), _lib.ptr(row_b), _lib.ptr(new),
                   _lib.stream())
         ctx.csr = csr
@@ -876,16 +875,16 @@ def _compress_index_sets(block, sp, p):
     if KEY_SETS and ns <= 64 and nw > 0:  # two launches (csrc/train_tok.hip) instead of ~35 framework ones
         total = torch.zeros(1, dtype=torch.int32, device=dev)
         cnt = torch.empty(nw, dtype=torch.int32, device=dev)
-        _lib.call("mssvt_train_list_counts", _i(nw), _i(ns), _lib.ptr(p.k_ind), _lib.ptr(cnt), _lib.ptr(total), _lib.stream())
+        _lib.call("mssvt_train_list_counts", nw, ns, _lib.ptr(p.k_ind), _lib.ptr(cnt), _lib.ptr(total), _lib.stream())
         P, = _read_sizes(total)  # one sync: the pair count (+ the pending words of the Blocks' index sets)
         koff = (torch.cumsum(cnt, 0, dtype=torch.int32) - cnt).contiguous()
         pair_vox = torch.empty(P, dtype=torch.int32, device=dev)
         pair_win = torch.empty(P, dtype=torch.int32, device=dev)
         geo = torch.empty((P, 8), dtype=torch.float32, device=dev)
         if P:
-            _lib.call("mssvt_train_pairs_compact", _i(nw), _i(ns), _lib.ptr(p.k_ind), _lib.ptr(p.win_vstart), _lib.ptr(koff),
-                      _lib.ptr(sp.indices), _lib.ptr(p.win_ind), fused._f3(sp.voxel_size), fused._f3(sp.point_cloud_range[0:3]),
-                      fused._f3(p.win_size_m), _lib.ptr(pair_vox), _lib.ptr(pair_win), _lib.ptr(geo), _lib.stream())
+            _lib.call("mssvt_train_pairs_compact", nw, ns, _lib.ptr(p.k_ind), _lib.ptr(p.win_vstart), _lib.ptr(koff),
+                      _lib.ptr(sp.indices), _lib.ptr(p.win_ind), _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3]),
+                      _lib.f3(p.win_size_m), _lib.ptr(pair_vox), _lib.ptr(pair_win), _lib.ptr(geo), _lib.stream())
         wins = dict(q_off=torch.arange(nw, dtype=torch.int32, device=dev), q_cnt=torch.ones(nw, dtype=torch.int32, device=dev),
                     k_off=koff, k_cnt=cnt)
         vox_csr = _gather_unique(pair_vox, N) if p.disjoint else Csr.gather(pair_vox, N)

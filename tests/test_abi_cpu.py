@@ -30,22 +30,128 @@ def test_library_builds_and_exports_declared_abi():
 
 
 def test_every_declared_entry_point_gets_its_argument_types():
-    """mssvt_amd._lib declares argtypes / restype of every entry point from the header (the fused path then hands plain
-    ints and addresses to ctypes): every declared symbol must be covered, with one ctypes type per parameter."""
+    """mssvt_amd._lib declares argtypes / restype of every entry point from the header (callers then hand plain ints,
+    floats and addresses to ctypes): every declared symbol must be covered, with one ctypes type per parameter and the
+    return type the header states."""
     from mssvt_amd import _lib
     lib = _lib.lib()
-    assert _lib.TYPED
     src = open(os.path.join(ROOT, "include", "mssvt_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    rets = {"long long": ctypes.c_longlong, "const char *": ctypes.c_char_p}
+    seen = {r: 0 for r in rets}
     for name in declared_symbols():
         fn = getattr(lib, name)
         assert fn.argtypes is not None, name
-        m = re.search(r"\b%s\s*\(([^;{]*?)\)\s*;" % name, src, flags=re.S)
-        params = m.group(1).strip()
+        m = re.search(r"\b(int|long long|const char \*)\s*%s\s*\(([^;{]*?)\)\s*;" % name, src, flags=re.S)
+        assert m is not None, name
+        params = m.group(2).strip()
         want = 0 if params in ("", "void") else params.count(",") + 1
         assert len(fn.argtypes) == want, (name, len(fn.argtypes), want)
+        if m.group(1) in rets:
+            assert fn.restype is rets[m.group(1)], (name, fn.restype)
+            seen[m.group(1)] += 1
+    assert seen["long long"] >= 10 and seen["const char *"] >= 1, seen
     assert lib.mssvt_ffn_packed_bytes(128, 256) == 2 * 2 * 128 * 256 * 2  # plain ints in, long long out
     assert lib.mssvt_hip_status_string(0) == b"ok"
+
+
+def test_missing_header_is_an_error_and_nothing_is_cached(monkeypatch):
+    from mssvt_amd import _lib
+    _lib.lib()  # the library is built
+    monkeypatch.setattr(_lib, "_lib", None)
+    monkeypatch.setattr(_lib, "HEADER_PATH", os.path.join(ROOT, "include", "no_such_header.h"))
+    try:
+        _lib.lib()
+    except _lib.MssvtHipError as e:
+        assert "no_such_header.h" in str(e)
+    else:
+        raise AssertionError("a missing header must raise")
+    assert _lib._lib is None
+
+
+def test_call_refuses_a_function_without_argument_types(monkeypatch):
+    """An exported function the header does not declare has no argtypes: a plain-int address handed to it would be cut
+    to 32 bits, so _lib.call refuses it before calling."""
+    from mssvt_amd import _lib
+    name = "mssvt_hip_abi_version"
+    calls = []
+
+    class Undeclared(object):
+        argtypes = None
+
+        def __call__(self, *args):
+            calls.append(args)
+            return 0
+
+    monkeypatch.setattr(_lib.lib(), name, Undeclared())
+    monkeypatch.delitem(_lib._fns, name, raising=False)
+    try:
+        _lib.call(name)
+    except _lib.MssvtHipError as e:
+        assert name in str(e)
+    else:
+        raise AssertionError("an undeclared function must be refused")
+    assert not calls and name not in _lib._fns
+    monkeypatch.undo()
+    fn = getattr(_lib.lib(), name)  # the same with the real function object
+    monkeypatch.setattr(fn, "argtypes", None)
+    monkeypatch.delitem(_lib._fns, name, raising=False)
+    try:
+        _lib.call(name)
+    except _lib.MssvtHipError:
+        pass
+    else:
+        raise AssertionError("an undeclared function must be refused")
+    assert name not in _lib._fns
+
+
+def test_package_passes_plain_values_only():
+    """One calling convention: no scalar or address of the package is wrapped in a ctypes object (host arrays and byref
+    out-parameters are the only ctypes values), and the names of the second convention are gone."""
+    import glob
+    patterns = [r"ctypes\.c_(int|float|longlong)\(", r"c_void_p\(.*data_ptr", r"TYPED|ptr_fast|_NULL", r"^_i ="]
+    for path in sorted(glob.glob(os.path.join(ROOT, "mssvt_amd", "*.py"))):
+        for no, line in enumerate(open(path), 1):
+            for pat in patterns:
+                assert not re.search(pat, line), "%s:%d matches %s" % (os.path.basename(path), no, pat)
+
+
+def header_parameter_counts():
+    src = open(os.path.join(ROOT, "include", "mssvt_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    out = {}
+    for name, params in re.findall(r"\b(mssvt_\w+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S):
+        params = params.strip()
+        out[name] = 0 if params in ("", "void") else params.count(",") + 1
+    return out
+
+
+def test_every_literal_call_site_passes_the_header_parameter_count():
+    """Each `_lib.call("<name>", ...)` of the package names a declared entry point and passes as many arguments as the
+    header has parameters.  Calls with a starred argument or a computed name cannot be counted here: there are 13 (11
+    starred, 2 computed names), and that number only grows on purpose."""
+    import ast
+    import glob
+    counts = header_parameter_counts()
+    checked, skipped = 0, []
+    for path in sorted(glob.glob(os.path.join(ROOT, "mssvt_amd", "*.py"))):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == "call"
+                    and isinstance(node.func.value, ast.Name) and node.func.value.id == "_lib" and node.args):
+                continue
+            where = "%s:%d" % (os.path.basename(path), node.lineno)
+            first = node.args[0]
+            if not (isinstance(first, ast.Constant) and isinstance(first.value, str)) or \
+                    any(isinstance(a, ast.Starred) for a in node.args) or node.keywords:
+                skipped.append(where)
+                continue
+            assert first.value in counts, "%s: %s is not declared in the header" % (where, first.value)
+            assert len(node.args) - 1 == counts[first.value], (where, first.value, len(node.args) - 1, counts[first.value])
+            checked += 1
+    print("call sites: %d checked, %d skipped" % (checked, len(skipped)))
+    assert checked >= 79, checked
+    assert len(skipped) <= 13, skipped
 
 
 def test_argument_errors_are_status_codes_not_exits():

@@ -591,7 +591,7 @@ def test_pair_set_kernels_match_the_framework_composition(nw, ns, N):
     geo = torch.empty((P, 8), dtype=torch.float32, device=DEV)
     if P:
         _lib.call("mssvt_train_pairs_compact", i(nw), i(ns), _lib.ptr(k_ind), _lib.ptr(vstart), _lib.ptr(off), _lib.ptr(indices),
-                  _lib.ptr(win_ind), fused._f3(vs), fused._f3(rng[:3]), fused._f3(wsz), _lib.ptr(pair_vox), _lib.ptr(pair_win),
+                  _lib.ptr(win_ind), _lib.f3(vs), _lib.f3(rng[:3]), _lib.f3(wsz), _lib.ptr(pair_vox), _lib.ptr(pair_win),
                   _lib.ptr(geo), _lib.stream())
     flat = torch.nonzero(valid.reshape(-1), as_tuple=True)[0]
     win = flat // ns

@@ -20,7 +20,7 @@ torch.manual_seed(0)
 net = config.build_backbone_from_cfg().to(dev).eval()
 _, _, vc, feats = bench.make_inputs(160000, 1, 0, dev)
 blk = net.backbone[0]
-_i, _P = ctypes.c_int, fused._P
+_i, _P = ctypes.c_int, _lib.addr
 with torch.no_grad():
     sp = SparseTensor(features=feats, indices=vc.int().contiguous(), spatial_shape=net.grid_size, voxel_size=net.voxel_size,
                       point_cloud_range=net.point_cloud_range, batch_size=1, hash_size=net.hash_size)
@@ -29,7 +29,7 @@ with torch.no_grad():
     x_in = sp.features.contiguous()
     C = x_in.shape[1]
     q_ind, nq, _ = fused._query(blk, p)
-    vs3, mn3 = fused._f3(sp.voxel_size), fused._f3(sp.point_cloud_range[0:3])
+    vs3, mn3 = _lib.f3(sp.voxel_size), _lib.f3(sp.point_cloud_range[0:3])
     tab = fused._interp_table(blk, sp, p, q_ind, nq, p.ind_win1, blk.max_num_win1, p.owner_win1, 1, vs3, mn3)
     abuf = fused._attn_buffer(p, nq, C, dev)
     abuf.normal_()
