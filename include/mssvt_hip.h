@@ -767,6 +767,27 @@ int mssvt_nms_normal(int num_boxes, const float *boxes_sorted, float thresh, voi
 int mssvt_boxes_pairwise(int mode, int num_a, const float *boxes_a, int stride_a, int num_b, const float *boxes_b,
                          int stride_b, float *out, void *stream);
 
+/* CenterHead's training targets of ONE head for the whole batch in one launch (ref: assign_target_of_single_head and the
+ * host loop around it, pcdet/models/dense_heads/center_head.py:103-158, :160-214; gaussian_radius /
+ * draw_gaussian_to_heatmap, pcdet/models/model_utils/centernet_utils.py:9-69).
+ * gt_boxes (B, num_boxes, code_size >= 8) f32 rows [x,y,z,dx,dy,dz,heading,...,label]; class_of_label (num_labels) int32:
+ * the class inside this head of label 0..num_labels-1, or -1 (label 0 = padding).  A row whose truncated label has a class
+ * takes the next slot of its sample, in row order; slots >= num_max_objs are dropped.  Per slot with finite values and
+ * positive dx, dy: the cell of the centre on the (H, W) map (x_min / y_min, voxel size and stride as the reference divides
+ * them, clamped into the map), CornerNet's radius (k1..k5: the constants 1 - ov, 1 + ov, 16 (1 - ov), -2 ov, 16 ov (ov - 1)
+ * of gaussian_radius, folded in double by the caller and rounded to float once, as torch folds them; truncated, at least
+ * min_radius), a (2 r + 1)^2 Gaussian with sigma = (2 r + 1) / 6 max-merged into heatmaps[b][class], and
+ *   target_boxes[b][slot] = [cx - ix, cy - iy, z, log dx, log dy, log dz, cos h, sin h, row[7 .. code_size-2]],
+ *   inds = iy * W + ix, masks = 1.  Any other slot (unused, zero extent, non-finite row): zero row, inds 0, masks 0.
+ * heatmaps (B, num_classes, H, W) f32, target_boxes (B, num_max_objs, code_size) f32, inds / masks (B, num_max_objs) i64:
+ * every element is written, once (no need to clear them); no host synchronisation, nothing read back.  num_boxes == 0 is
+ * legal (all zero).  B, num_classes <= 65535, H, W <= 2^20; radii are cut at 2^20 cells.                              */
+int mssvt_center_targets(int batch_size, int num_boxes, int code_size, const float *gt_boxes, const int *class_of_label,
+                         int num_labels, int num_classes, int H, int W, int num_max_objs, float x_min, float y_min,
+                         float voxel_x, float voxel_y, float stride, float k1, float k2, float k3, float k4, float k5,
+                         int min_radius, float *heatmaps, float *target_boxes, long long *inds, long long *masks,
+                         void *stream);
+
 /* Weight / bias gradient of an nn.Linear over compact rows (training path; what autograd's library GEMM computes for
  * the reference's to_qs / to_kvs / projs / linear1 / linear2, ref mssvt_utils.py:80-83, mssvt_backbone.py:25-27):
  *   dW (Cout,Cin) = dY^T X,  db (Cout) = column sums of dY (db may be NULL);  X (M,Cin), dY (M,Cout) f32 row-major.

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 from torch import nn
 
-from . import iou3d_nms_utils
+from . import _lib, iou3d_nms_utils
 
 
 def _get(cfg, key, default=None):
@@ -127,6 +127,33 @@ def splat_gaussian(heatmap, cx, cy, radius):
         torch.max(region, patch, out=region)
 
 
+def center_targets(gt_boxes, class_of_label, num_classes, feature_map_size, point_cloud_range, voxel_size,
+                   feature_map_stride, num_max_objs=500, gaussian_overlap=0.1, min_radius=2):
+    """The training targets of ONE head for the whole batch in one launch (csrc/center_targets.hip): what
+    ``CenterHead.assign_target_of_single_head`` computes per sample on the host (ref center_head.py:103-158,
+    centernet_utils.py:9-69), without a copy or a synchronisation.  gt_boxes (B, N, 8+) on the device, label last;
+    class_of_label (C + 1) int32 on the device: the class inside the head of label 0..C or -1 (``CenterHead.label_tables``);
+    feature_map_size (H, W).  Returns heatmap (B, num_classes, H, W) f32, target_boxes (B, M, 8+) f32, inds and mask
+    (B, M) i64.  Rows with a non-finite value get no target and a label outside 0..C takes no slot (the host path raises)."""
+    if not (gt_boxes.is_cuda and gt_boxes.dim() == 3):
+        raise _lib.MssvtHipError("center_targets needs (B, N, 8+) boxes on the GPU")
+    boxes = gt_boxes.detach().float().contiguous()
+    B, N, D = boxes.shape
+    H, W = int(feature_map_size[0]), int(feature_map_size[1])
+    M, ov = int(num_max_objs), float(gaussian_overlap)
+    heatmap = torch.empty((B, int(num_classes), H, W), dtype=torch.float32, device=boxes.device)
+    target_boxes = torch.empty((B, M, D), dtype=torch.float32, device=boxes.device)
+    inds = torch.empty((B, M), dtype=torch.int64, device=boxes.device)
+    mask = torch.empty((B, M), dtype=torch.int64, device=boxes.device)
+    # the constants of gaussian_radius: Python-scalar sub-expressions, folded in double and rounded to float32 once
+    _lib.call("mssvt_center_targets", B, N, D, boxes.data_ptr(), _lib.ptr(class_of_label), class_of_label.numel(),
+              int(num_classes), H, W, M, float(point_cloud_range[0]), float(point_cloud_range[1]), float(voxel_size[0]),
+              float(voxel_size[1]), float(feature_map_stride), 1.0 - ov, 1.0 + ov, 16.0 * (1.0 - ov), -2.0 * ov,
+              16.0 * ov * (ov - 1.0), int(min_radius), _lib.ptr(heatmap), _lib.ptr(target_boxes), _lib.ptr(inds),
+              _lib.ptr(mask), _lib.stream())
+    return heatmap, target_boxes, inds, mask
+
+
 def centernet_focal_loss(pred, gt):
     """ref loss_utils.py:264-299 (CornerNet's penalty-reduced focal loss): pred = clamped sigmoid, gt = Gaussian heat map."""
     pos = gt.eq(1).float()
@@ -178,6 +205,29 @@ class CenterHead(nn.Module):
         self.predict_boxes_when_training = predict_boxes_when_training
         self.forward_ret_dict = {}
         self.nms_fn = None  # test hook: an alternative NMS with the signature of iou3d_nms_utils.nms_gpu
+        self._label_tables_dev = {}  # device -> label_tables() as an int32 tensor (heads, C + 1)
+
+    def label_tables(self):
+        """int array [label 0..C][head]: the class inside the head that a box of that label gets, or -1 when the head
+        does not take it.  Simulates the re-labelling of ``assign_targets`` (ref :190-193): a box that head h takes has its
+        label overwritten with its index inside h + 1, and the FOLLOWING heads look that number up in the global class
+        list again -- with heads [[Pedestrian], [Vehicle, Cyclist]] a Pedestrian also lands in head 1 as class 0."""
+        names = ["bg"] + self.class_names
+        table = np.full((len(names), len(self.class_names_each_head)), -1, dtype=np.int32)
+        for label in range(len(names)):
+            cur = label
+            for h, head_names in enumerate(self.class_names_each_head):
+                if names[cur] in head_names:
+                    table[label, h] = head_names.index(names[cur])
+                    cur = int(table[label, h]) + 1
+        return table
+
+    def _label_table_on(self, device):
+        t = self._label_tables_dev.get(device)
+        if t is None:
+            t = torch.from_numpy(np.ascontiguousarray(self.label_tables().T)).to(device)
+            self._label_tables_dev[device] = t
+        return t
 
     def generate_predicted_boxes(self, batch_size, pred_dicts):
         post = _get(self.model_cfg, "POST_PROCESSING")
@@ -255,7 +305,33 @@ class CenterHead(nn.Module):
         """gt_boxes (B, M, 8+) with the class id (1-based over class_names, 0 = padding) last; feature_map_size (H, W)
         -> per head: heatmaps (B, c, H, W), target_boxes (B, M', 8+), inds / masks (B, M')  (ref :160-214).  As in the
         reference a box reaches a head with its class re-numbered inside that head, and the re-numbering is written into the
-        working copy of the boxes that the FOLLOWING heads read their class names from (ref :190-193)."""
+        working copy of the boxes that the FOLLOWING heads read their class names from (ref :190-193).
+        On the device the targets of a head are one launch (``assign_targets_device``); ``assign_targets_host`` is the CPU
+        statement of the same semantics."""
+        if gt_boxes.is_cuda:
+            return self.assign_targets_device(gt_boxes, feature_map_size)
+        return self.assign_targets_host(gt_boxes, feature_map_size)
+
+    def assign_targets_device(self, gt_boxes, feature_map_size):
+        """``center_targets`` per head with the head's column of ``label_tables``: nothing is read back, the caller's boxes
+        are only read."""
+        tcfg = _get(self.model_cfg, "TARGET_ASSIGNER_CONFIG")
+        out = dict(heatmaps=[], target_boxes=[], inds=[], masks=[], heatmap_masks=[])
+        tables = self._label_table_on(gt_boxes.device)
+        for h, head_names in enumerate(self.class_names_each_head):
+            res = center_targets(
+                gt_boxes, tables[h], len(head_names), feature_map_size, self.point_cloud_range, self.voxel_size,
+                _get(tcfg, "FEATURE_MAP_STRIDE"), num_max_objs=_get(tcfg, "NUM_MAX_OBJS"),
+                gaussian_overlap=_get(tcfg, "GAUSSIAN_OVERLAP"), min_radius=_get(tcfg, "MIN_RADIUS"))
+            out["heatmaps"].append(res[0].to(gt_boxes.dtype))
+            out["target_boxes"].append(res[1].to(gt_boxes.dtype))
+            out["inds"].append(res[2])
+            out["masks"].append(res[3])
+        return out
+
+    def assign_targets_host(self, gt_boxes, feature_map_size):
+        """The per-sample host loop of the reference (ref :160-214): boxes of any device, every sample's targets computed
+        on the CPU and moved to the boxes' device."""
         size_xy = list(feature_map_size)[::-1]
         tcfg = _get(self.model_cfg, "TARGET_ASSIGNER_CONFIG")
         work = gt_boxes.clone()
