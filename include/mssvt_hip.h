@@ -788,6 +788,49 @@ int mssvt_center_targets(int batch_size, int num_boxes, int code_size, const flo
                          int min_radius, float *heatmaps, float *target_boxes, long long *inds, long long *masks,
                          void *stream);
 
+/* CenterHead's inference decode of ONE head for the whole batch (ref: decode_bbox_from_heatmap / _topk,
+ * pcdet/models/model_utils/centernet_utils.py:136-216), a fixed number of launches (8) whatever B is; no host
+ * synchronisation, nothing read back.  All maps f32 contiguous NCHW: hm (B, C, H, W) RAW logits, center (B, 2, H, W),
+ * center_z (B, 1, H, W), dim (B, 3, H, W) raw log sizes, rot (B, 2, H, W) [cos, sin], vel (B, num_vel, H, W) or NULL with
+ * num_vel = 0.
+ * Selection: per sample the N = C H W cells are ranked by (logit descending, flat index c H W + y W + x ascending) and the
+ * first K' = min(K, N) are taken -- exact for any input, run-to-run deterministic.  The order refines topk(sigmoid(hm))
+ * wherever that is defined (sigmoid is monotone, equal scores are unordered there).  -0.0 and +0.0 compare equal (the
+ * index decides); a NaN logit ranks below everything and never yields a box.
+ * Decode of a selected cell (c, y, x) with logit l, in rank order, one rounded f32 operation per step:
+ *   score = 1 / (1 + exp(-l));  bx = ((x + center[0]) * stride) * voxel_x + x_min;  by likewise with y, center[1], voxel_y,
+ *   y_min;  z = center_z;  sizes = exp(dim[0..2]);  heading = atan2(rot[1], rot[0]);  vel[0..num_vel) copied.
+ * Filter: kept iff limit_*_min <= (bx, by, z) <= limit_*_max (inclusive, a NaN fails) and, with has_score_thresh != 0,
+ * score > score_thresh (strict).  Survivors are compacted in rank order into cand_boxes (B, K, 7 + num_vel) f32,
+ * cand_scores (B, K) f32, cand_labels (B, K) i32 (the class inside the head), cand_num (B) i32; EVERY element is written,
+ * the tails are zero.  workspace: mssvt_center_decode_workspace_bytes(...) bytes (0: shape refused), the caller's, cleared
+ * by the call on `stream` -- no static device state, concurrent calls on different streams need different workspaces.
+ * Limits: B <= 65535, C <= 255, C H W < 2^24, K <= MSSVT_CENTER_DECODE_MAX_K, num_vel <= 64; MSSVT_E_TOOLARGE beyond. */
+#define MSSVT_CENTER_DECODE_MAX_K 4096
+long long mssvt_center_decode_workspace_bytes(int batch_size, int num_classes, int H, int W, int K);
+int mssvt_center_decode(int batch_size, int num_classes, int H, int W, int num_vel, const float *hm, const float *center,
+                        const float *center_z, const float *dim, const float *rot, const float *vel, int K, float stride,
+                        float voxel_x, float voxel_y, float x_min, float y_min, float limit_x_min, float limit_y_min,
+                        float limit_z_min, float limit_x_max, float limit_y_max, float limit_z_max, int has_score_thresh,
+                        float score_thresh, void *workspace, float *cand_boxes, float *cand_scores, int *cand_labels,
+                        int *cand_num, void *stream);
+
+/* The NMS of mssvt_nms_bev / mssvt_nms_normal (`normal` != 0) for a batch of padded candidate lists whose lengths live on
+ * the device (the outputs of mssvt_center_decode): two launches whose sizes depend on K and pre_max only, nothing read back.
+ * Per sample b: n = min(cand_num[b], pre_max) rows of cand_boxes[b] (K rows of row_floats >= 7 floats, descending score);
+ * a box suppresses every LATER box with IoU > thresh (strict; the pair geometry of the unbatched entries).  With
+ * base = out_num[b] ON ENTRY, the first min(kept, post_max, out_rows - base) kept rows j go to out_boxes[b][base + j]
+ * (out_rows rows of row_floats floats per sample), out_scores[b][base + j] and out_labels[b][base + j] =
+ * class_map[cand_label] + 1 (i64; class_map (num_classes) i64; a label outside it gives 0), and out_num[b] grows by their
+ * number: calls for successive heads on one stream append head-major.  Rows at or beyond out_num[b] are not touched (the
+ * caller zeroes the buffers once).  workspace: mssvt_nms_bev_batched_workspace_bytes(B, K, pre_max) bytes, no need to
+ * clear it.  B <= 65535, K <= 4096; MSSVT_E_TOOLARGE beyond. */
+long long mssvt_nms_bev_batched_workspace_bytes(int batch_size, int K, int pre_max);
+int mssvt_nms_bev_batched(int batch_size, int K, int row_floats, const float *cand_boxes, const float *cand_scores,
+                          const int *cand_labels, const int *cand_num, const long long *class_map, int num_classes,
+                          int pre_max, int post_max, float thresh, int normal, void *workspace, int out_rows,
+                          float *out_boxes, float *out_scores, long long *out_labels, int *out_num, void *stream);
+
 /* Weight / bias gradient of an nn.Linear over compact rows (training path; what autograd's library GEMM computes for
  * the reference's to_qs / to_kvs / projs / linear1 / linear2, ref mssvt_utils.py:80-83, mssvt_backbone.py:25-27):
  *   dW (Cout,Cin) = dY^T X,  db (Cout) = column sums of dY (db may be NULL);  X (M,Cin), dY (M,Cout) f32 row-major.

@@ -98,6 +98,61 @@ def decode_bbox_from_heatmap(heatmap, rot_cos, rot_sin, center, center_z, dim, p
             for b in range(B)]
 
 
+CENTER_DECODE_MAX_K = 4096  # include/mssvt_hip.h MSSVT_CENTER_DECODE_MAX_K
+
+
+def center_decode(hm, center, center_z, dim, rot, vel=None, *, point_cloud_range, voxel_size, feature_map_stride, K=100,
+                  score_thresh=None, post_center_limit_range):
+    """``decode_bbox_from_heatmap`` of ONE head for the whole batch on the device (csrc/center_decode.hip), a fixed number
+    of launches and no host synchronisation.  hm (B, C, H, W) RAW logits, dim the raw log sizes, rot [cos, sin]; other
+    float dtypes are converted.  The cells are ranked by (logit descending, flat index ascending) -- exact and
+    deterministic, a refinement of ``topk(sigmoid(hm))``; a NaN logit never yields a box.  Returns the survivors of the
+    centre-range / score filters in rank order, padded: cand_boxes (B, K, 7 + V) f32, cand_scores (B, K) f32,
+    cand_labels (B, K) i32 (class inside the head), cand_num (B) i32; the tails are zero."""
+    maps = [hm, center, center_z, dim, rot] + ([vel] if vel is not None else [])
+    if not all(t.is_cuda and t.dim() == 4 for t in maps):
+        raise _lib.MssvtHipError("center_decode needs (B, C, H, W) maps on the GPU (no CPU path)")
+    maps = [t.detach().float().contiguous() for t in maps]
+    hm, center, center_z, dim, rot = maps[:5]
+    vel = maps[5] if vel is not None else None
+    B, C, H, W = (int(v) for v in hm.shape)
+    V = int(vel.shape[1]) if vel is not None else 0
+    for t, c in ((center, 2), (center_z, 1), (dim, 3), (rot, 2)) + (((vel, V),) if V else ()):
+        if tuple(t.shape) != (B, c, H, W) or t.device != hm.device:
+            raise _lib.MssvtHipError("center_decode: a regression map is not (%d, %d, %d, %d) on the heat map's device" % (B, c, H, W))
+    K = int(K)
+    if K < 0:
+        raise _lib.MssvtHipError("center_decode: K = %d is negative" % K)
+    dev = hm.device
+    if min(B, C, H, W, K) == 0:  # an empty batch / map / K: nothing to select, no launch
+        return (torch.zeros((B, K, 7 + V), dtype=torch.float32, device=dev), torch.zeros((B, K), dtype=torch.float32, device=dev),
+                torch.zeros((B, K), dtype=torch.int32, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev))
+    nbytes = int(_lib.lib().mssvt_center_decode_workspace_bytes(B, C, H, W, K))
+    if nbytes <= 0:
+        raise _lib.MssvtHipError("center_decode: shape beyond the kernel's limits (B <= 65535, C <= 255, C H W < 2^24, "
+                                 "K <= %d): B=%d C=%d H=%d W=%d K=%d" % (CENTER_DECODE_MAX_K, B, C, H, W, K))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)  # cleared by the call, on this stream
+    cand_boxes = torch.empty((B, K, 7 + V), dtype=torch.float32, device=dev)  # all four fully written by the call
+    cand_scores = torch.empty((B, K), dtype=torch.float32, device=dev)
+    cand_labels = torch.empty((B, K), dtype=torch.int32, device=dev)
+    cand_num = torch.empty((B,), dtype=torch.int32, device=dev)
+    lim = [float(v) for v in post_center_limit_range]
+    _lib.call("mssvt_center_decode", B, C, H, W, V, hm.data_ptr(), center.data_ptr(), center_z.data_ptr(), dim.data_ptr(),
+              rot.data_ptr(), _lib.ptr(vel), K, float(feature_map_stride), float(voxel_size[0]), float(voxel_size[1]),
+              float(point_cloud_range[0]), float(point_cloud_range[1]), lim[0], lim[1], lim[2], lim[3], lim[4], lim[5],
+              0 if score_thresh is None else 1, 0.0 if score_thresh is None else float(score_thresh), _lib.ptr(ws),
+              _lib.ptr(cand_boxes), _lib.ptr(cand_scores), _lib.ptr(cand_labels), _lib.ptr(cand_num), _lib.stream())
+    return cand_boxes, cand_scores, cand_labels, cand_num
+
+
+def unpad(padded):
+    """The list of per-sample dicts that ``generate_predicted_boxes`` returns, from the padded dict of
+    ``generate_predicted_boxes_padded``: ONE read-back (``num``) for the whole batch."""
+    nums = padded["num"].tolist()
+    return [dict(pred_boxes=padded["pred_boxes"][b, :n], pred_scores=padded["pred_scores"][b, :n],
+                 pred_labels=padded["pred_labels"][b, :n]) for b, n in enumerate(nums)]
+
+
 def gaussian_radius(height, width, min_overlap):
     """CornerNet's radius: the smallest of the three roots that keep a shifted box above `min_overlap` IoU
     (ref centernet_utils.py:9-35); vectorised over the objects."""
@@ -206,6 +261,8 @@ class CenterHead(nn.Module):
         self.forward_ret_dict = {}
         self.nms_fn = None  # test hook: an alternative NMS with the signature of iou3d_nms_utils.nms_gpu
         self._label_tables_dev = {}  # device -> label_tables() as an int32 tensor (heads, C + 1)
+        self._class_maps_dev = {}  # device -> _class_maps on that device (generate_predicted_boxes_padded)
+        self.padded_predictions = False  # eval forward: final_box_padded (no host sync) instead of final_box_dicts
 
     def label_tables(self):
         """int array [label 0..C][head]: the class inside the head that a box of that label gets, or -1 when the head
@@ -268,6 +325,57 @@ class CenterHead(nn.Module):
             ret[k]["pred_scores"] = torch.cat(ret[k]["pred_scores"], dim=0)
             ret[k]["pred_labels"] = torch.cat(ret[k]["pred_labels"], dim=0) + 1
         return ret
+
+    def _class_maps_on(self, device):
+        maps = self._class_maps_dev.get(device)
+        if maps is None:
+            maps = [m.to(device).contiguous() for m in self._class_maps]
+            self._class_maps_dev[device] = maps
+        return maps
+
+    def generate_predicted_boxes_padded(self, batch_size, pred_dicts):
+        """``generate_predicted_boxes`` without a host synchronisation or a read-back: per head ``center_decode`` (top-K,
+        decode, filters) and ``iou3d_nms_utils.nms_padded`` (NMS with the counts on the device), each head appended behind
+        the one before it.  Same config keys; returns pred_boxes (B, P, 7 + V) f32, pred_scores (B, P) f32, pred_labels
+        (B, P) i64 (1-based over class_names, 0 in the padding) and num (B) i32 with P = heads x NMS_POST_MAXSIZE;
+        ``unpad`` turns them into the list.  Covers NMS_TYPE nms_gpu / nms_normal_gpu with one threshold; per-class
+        thresholds, a custom ``nms_fn`` or MAX_OBJ_PER_SAMPLE beyond the kernel's limit stay with the list path."""
+        post = _get(self.model_cfg, "POST_PROCESSING")
+        nms_cfg = _get(post, "NMS_CONFIG")
+        dev = pred_dicts[0]["hm"].device
+        if dev.type != "cuda":
+            raise _lib.MssvtHipError("generate_predicted_boxes_padded runs on the GPU only (no CPU path); "
+                                     "generate_predicted_boxes takes CPU tensors")
+        thr = _get(nms_cfg, "NMS_THRESH")
+        if isinstance(thr, (list, tuple)):
+            if len(thr) != 1:
+                raise _lib.MssvtHipError("generate_predicted_boxes_padded: per-class NMS_THRESH (%d entries) is not "
+                                         "covered, use generate_predicted_boxes" % len(thr))
+            thr = thr[0]
+        if self.nms_fn is not None:
+            raise _lib.MssvtHipError("generate_predicted_boxes_padded: a custom nms_fn is not covered, use generate_predicted_boxes")
+        nms_type = _get(nms_cfg, "NMS_TYPE")
+        if nms_type not in ("nms_gpu", "nms_normal_gpu"):
+            raise _lib.MssvtHipError("generate_predicted_boxes_padded: NMS_TYPE %s is not covered (nms_gpu, nms_normal_gpu)" % nms_type)
+        K = int(_get(post, "MAX_OBJ_PER_SAMPLE"))
+        if K > CENTER_DECODE_MAX_K:
+            raise _lib.MssvtHipError("generate_predicted_boxes_padded: MAX_OBJ_PER_SAMPLE %d exceeds the kernel's limit %d, "
+                                     "use generate_predicted_boxes" % (K, CENTER_DECODE_MAX_K))
+        has_vel = "vel" in list(_get(self.separate_head_cfg, "HEAD_ORDER"))
+        post_max = int(_get(nms_cfg, "NMS_POST_MAXSIZE"))
+        cmaps = self._class_maps_on(dev)
+        out = None
+        for idx, pd in enumerate(pred_dicts):
+            cand = center_decode(
+                pd["hm"], pd["center"], pd["center_z"], pd["dim"], pd["rot"], pd["vel"] if has_vel else None,
+                point_cloud_range=self.point_cloud_range, voxel_size=self.voxel_size,
+                feature_map_stride=self.feature_map_stride, K=K, score_thresh=_get(post, "SCORE_THRESH"),
+                post_center_limit_range=list(_get(post, "POST_CENTER_LIMIT_RANGE")))
+            if out is None:
+                out = iou3d_nms_utils.padded_outputs(int(batch_size), len(pred_dicts) * post_max, cand[0].shape[2], dev)
+            iou3d_nms_utils.nms_padded(*cand, cmaps[idx], float(thr), int(_get(nms_cfg, "NMS_PRE_MAXSIZE")), post_max,
+                                       normal=nms_type == "nms_normal_gpu", out=out)
+        return out
 
     def assign_target_of_single_head(self, num_classes, gt_boxes, feature_map_size, feature_map_stride, num_max_objs=500,
                                      gaussian_overlap=0.1, min_radius=2):
@@ -380,6 +488,10 @@ class CenterHead(nn.Module):
                 data_dict["gt_boxes"], feature_map_size=data_dict["spatial_features_2d"].shape[2:])
         self.forward_ret_dict["pred_dicts"] = pred_dicts
         if not self.training or self.predict_boxes_when_training:
+            if self.padded_predictions and not self.training:
+                with torch.no_grad():
+                    data_dict["final_box_padded"] = self.generate_predicted_boxes_padded(data_dict["batch_size"], pred_dicts)
+                return data_dict
             with torch.no_grad():
                 boxes = self.generate_predicted_boxes(data_dict["batch_size"], pred_dicts)
             if self.training:

@@ -20,7 +20,7 @@ from torch import nn
 
 from .base_bev_backbone import BaseBEVBackbone
 from . import iou3d_nms_utils
-from .center_head import CenterHead
+from .center_head import CenterHead, unpad
 from .dynamic_vfe import DynamicVFE
 from .height_compression import HeightCompression
 from .mssvt_backbone import MixedScaleSparseTransformer
@@ -123,6 +123,9 @@ class CenterPoint(nn.Module):
 
     def post_processing(self, batch_dict):
         """(pred_dicts, recall_dict), ref centerpoint.py:36-50; recall_dict stays {} without ground truth in the batch."""
+        if "final_box_dicts" not in batch_dict and "final_box_padded" in batch_dict:
+            # CenterHead.padded_predictions: the head's decode ran without a host sync, the lists cost one read-back here
+            batch_dict["final_box_dicts"] = unpad(batch_dict["final_box_padded"])
         final_pred_dict = batch_dict["final_box_dicts"]
         recall_dict = {}
         if "gt_boxes" not in batch_dict:

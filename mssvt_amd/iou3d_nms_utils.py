@@ -102,6 +102,55 @@ def boxes_iou3d_gpu(boxes_a, boxes_b):
     return boxes_pairwise(BOX_IOU_3D, boxes_a, boxes_b)
 
 
+def padded_outputs(batch_size, rows, row_floats, device):
+    """The zeroed padded outputs that ``nms_padded`` appends into: pred_boxes (B, rows, row_floats) f32, pred_scores
+    (B, rows) f32, pred_labels (B, rows) i64, num (B) i32."""
+    return dict(pred_boxes=torch.zeros((batch_size, rows, row_floats), dtype=torch.float32, device=device),
+                pred_scores=torch.zeros((batch_size, rows), dtype=torch.float32, device=device),
+                pred_labels=torch.zeros((batch_size, rows), dtype=torch.int64, device=device),
+                num=torch.zeros((batch_size,), dtype=torch.int32, device=device))
+
+
+def nms_padded(cand_boxes, cand_scores, cand_labels, cand_num, class_map, thresh, pre_maxsize, post_maxsize, normal=False,
+               out=None):
+    """Greedy NMS of a batch of padded candidate lists (the outputs of ``center_head.center_decode``: rows in descending
+    score order, cand_num (B) i32 of them valid) with the counts on the device: two launches, no host synchronisation
+    (csrc/nms_bev_batched.hip).  Per sample the first min(cand_num, pre_maxsize) rows meet; the first post_maxsize kept rows
+    are APPENDED to `out` (``padded_outputs``; made with post_maxsize rows when None) behind its ``num`` rows, labels as
+    class_map[label] + 1 (class_map (C) i64 on the device); `normal`: the axis-aligned IoU of ``nms_normal_gpu``.
+    Returns `out`."""
+    if not (cand_boxes.is_cuda and cand_boxes.dim() == 3 and cand_boxes.shape[2] >= 7):
+        raise _lib.MssvtHipError("nms_padded needs (B, K, 7+) candidate boxes on the GPU (no CPU path)")
+    B, K, D = (int(v) for v in cand_boxes.shape)
+    dev = cand_boxes.device
+    if out is None:
+        out = padded_outputs(B, int(post_maxsize), D, dev)
+    P = int(out["pred_boxes"].shape[1])
+    ok = (cand_boxes.dtype == torch.float32 and cand_scores.dtype == torch.float32 and cand_labels.dtype == torch.int32 and
+          cand_num.dtype == torch.int32 and class_map.dtype == torch.int64 and tuple(cand_scores.shape) == (B, K) and
+          tuple(cand_labels.shape) == (B, K) and tuple(cand_num.shape) == (B,) and class_map.dim() == 1 and
+          tuple(out["pred_boxes"].shape) == (B, P, D) and out["pred_boxes"].dtype == torch.float32 and
+          tuple(out["pred_scores"].shape) == (B, P) and out["pred_scores"].dtype == torch.float32 and
+          tuple(out["pred_labels"].shape) == (B, P) and out["pred_labels"].dtype == torch.int64 and
+          tuple(out["num"].shape) == (B,) and out["num"].dtype == torch.int32 and
+          all(t.device == dev for t in (cand_scores, cand_labels, cand_num, class_map, *out.values())))
+    if not ok:
+        raise _lib.MssvtHipError("nms_padded: candidates f32 (B, K, D) / f32 (B, K) / i32 (B, K) / i32 (B), class_map i64 (C) "
+                                 "and outputs f32 (B, P, D) / f32 (B, P) / i64 (B, P) / i32 (B) must share one device")
+    if B == 0 or K == 0:
+        return out
+    nbytes = int(_lib.lib().mssvt_nms_bev_batched_workspace_bytes(B, K, int(pre_maxsize)))
+    if nbytes <= 0:
+        raise _lib.MssvtHipError("nms_padded: beyond the kernel's limits (B <= 65535, K <= 4096, pre_maxsize >= 1): "
+                                 "B=%d K=%d pre_maxsize=%d" % (B, K, int(pre_maxsize)))
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    _lib.call("mssvt_nms_bev_batched", B, K, D, _lib.ptr(cand_boxes), _lib.ptr(cand_scores), _lib.ptr(cand_labels),
+              _lib.ptr(cand_num), _lib.ptr(class_map), int(class_map.numel()), int(pre_maxsize), int(post_maxsize),
+              float(thresh), 1 if normal else 0, _lib.ptr(ws), P, _lib.ptr(out["pred_boxes"]), _lib.ptr(out["pred_scores"]),
+              _lib.ptr(out["pred_labels"]), _lib.ptr(out["num"]), _lib.stream())
+    return out
+
+
 def _nms_sorted(b, thresh, entry="mssvt_nms_bev"):
     """Indices (into `b`, best first) that greedy NMS keeps among boxes already sorted by descending score."""
     n = int(b.shape[0])

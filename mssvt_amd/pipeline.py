@@ -105,6 +105,8 @@ def _tensors_of(out):
                 t = getattr(v, name, None)
                 if isinstance(t, torch.Tensor) and t.is_cuda:
                     seen.append(t)
+        elif isinstance(v, dict):  # a dict of tensors: CenterHead's `final_box_padded`
+            seen.extend(t for t in v.values() if isinstance(t, torch.Tensor) and t.is_cuda)
     return seen
 
 
