@@ -247,7 +247,7 @@ int mssvt_level_setup_sorted_pillars(
  * even / win1 entries per window.  indices (N,4) voxel coords.  With the metadata asked for, the list rows ind_*, the key
  * indices / masks k_ind* / k_mask* and the owner_* arrays may each be NULL (the fused consumers read the metadata and the
  * interpolation tables: mssvt_frame_forward passes none of them); the weights of the tables use the hardware's square root
- * and reciprocal (1 ulp each).
+ * and reciprocal (1 ulp each); a voxel with a single candidate (a query list of one slot) gets the weight 1 exactly.
  * column_vbase / level_status_dev (optional, with occ_columns; from mssvt_level_setup_sorted): for a voxel list sorted
  * by (b,x,y,z) the index of an occupied cell is column_vbase + popcount(column word below z) and the hash is not
  * probed at all (xyz_to_vidx may then be NULL); when level_status_dev[0] has ST_UNSORTED (8) set the hash is used.
@@ -323,7 +323,8 @@ int mssvt_occupancy_columns(const int *indices, int num_voxels, int batch_size, 
 
 /* Work order and compact query rows for mssvt_block_attention_group, from one row of the
  * plan's (3,cap) nq_valid (odd / even / win1) and that list's qmeta (cap,nq,4):
- *   perm (cap)          the windows with >= 1 valid query, sorted by descending nq_valid;
+ *   perm (cap)          the windows with >= 1 valid query, sorted by descending min(nq_valid, 256) (a counting sort:
+ *                       every window with >= 256 queries shares the first bucket; the order inside a bucket is free);
  *   num_active_dev      how many;
  *   q_off (cap)         exclusive prefix sum of nq_valid in window order = first compact
  *                       query row of each window;

@@ -153,6 +153,7 @@ __device__ __forceinline__ void vt_block(const VtArgs &a, const int blk) {
     float w1 = __builtin_amdgcn_rcpf(d1), w2 = __builtin_amdgcn_rcpf(d2), w3 = __builtin_amdgcn_rcpf(d3);
     const float rnorm = __builtin_amdgcn_rcpf((w1 + w2) + w3);
     w1 *= rnorm; w2 *= rnorm; w3 *= rnorm;
+    if (c2 < 0) w1 = 1.f;  // one candidate (nq == 1): the reference's w / w is exactly 1, rcp(w) * w need not be
     if (c1 < 0 || c1 >= nvl) w1 = 0.f;  // empty slots carry zero features
     if (c2 < 0 || c2 >= nvl) w2 = 0.f;
     if (c3 < 0 || c3 >= nvl) w3 = 0.f;

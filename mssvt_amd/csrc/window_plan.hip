@@ -577,6 +577,7 @@ __global__ void __launch_bounds__(PLAN_MAX_WPB *MSSVT_WAVE, FPS_TPL <= 4 ? PLAN_
                     float w1 = __builtin_amdgcn_rcpf(d1), w2 = __builtin_amdgcn_rcpf(d2), w3 = __builtin_amdgcn_rcpf(d3);
                     const float rnorm = __builtin_amdgcn_rcpf((w1 + w2) + w3);
                     w1 *= rnorm; w2 *= rnorm; w3 *= rnorm;
+                    if (c2 < 0) w1 = 1.f;  // one candidate (nq == 1): the reference's w / w is exactly 1, rcp(w) * w need not be
                     if (!(m1 & 1) || c1 < 0) w1 = 0.f;  // empty slots carry zero features
                     if (!(m2 & 1) || c2 < 0) w2 = 0.f;
                     if (!(m3 & 1) || c3 < 0) w3 = 0.f;

@@ -195,14 +195,21 @@ def gather_operation(features, idx):
     return out
 
 
-def three_nn(unknown, known):
-    """pointnet2_utils.py:79-99 (ThreeNN.forward) -> K9; returns (sqrt(dist2), idx)."""
+def three_nn_sq(unknown, known):
+    """K9 itself (interpolate_gpu.cu:16-59): (float32 SQUARED distances, idx) as the kernel leaves them."""
     unknown, known = _f32(unknown), _f32(known)
     B, N, _ = unknown.shape
     m = known.shape[1]
     dist2 = np.zeros((B, N, 3), dtype=np.float32)
     idx = np.zeros((B, N, 3), dtype=np.int32)
-    lib().orc_three_nn(B, N, m, _fp(unknown), _fp(known), _fp(dist2), _ip(idx))
+    if B * N:
+        lib().orc_three_nn(B, N, m, _fp(unknown), _fp(known), _fp(dist2), _ip(idx))
+    return dist2, idx
+
+
+def three_nn(unknown, known):
+    """pointnet2_utils.py:79-99 (ThreeNN.forward) -> K9; returns (sqrt(dist2), idx)."""
+    dist2, idx = three_nn_sq(unknown, known)
     return np.sqrt(dist2), idx
 
 

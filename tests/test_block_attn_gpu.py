@@ -475,23 +475,15 @@ class OnGpu(object):
         self._blobs = None
 
     def check_plan_order(self):
-        """mssvt_plan_order against torch on the same arrays (include/mssvt_hip.h:324-336)."""
+        """mssvt_plan_order against the statement of its contract (tests/window_plan_ref.py; include/mssvt_hip.h:324-336) on the
+        same arrays.  nq <= 256 here, so min(nq_valid, 256) is nq_valid itself."""
+        from tests.window_plan_ref import check_plan_order
         c = self.case
-        nqv = c.nq_valid[:c.nw].long()
-        total = int(nqv.sum())
-        assert torch.equal(self.q_off[:c.nw].cpu().long(), nqv.cumsum(0) - nqv)
-        fits = nqv.cumsum(0) <= self.row_cap
-        kept = int(nqv[fits].sum())  # rows of the windows that fit the capacity
-        assert int(self.n_rows.item()) == (total if total <= self.row_cap else kept)
-        n_act = int(self.n_act.item())
-        assert n_act == int((nqv > 0).sum())
-        perm = self.perm[:n_act].cpu().long()
-        assert torch.equal(perm.sort().values, (nqv > 0).nonzero()[:, 0])
-        assert bool((nqv[perm][1:] <= nqv[perm][:-1]).all())
-        w, s = (row_bits(c.qmeta[:c.nw]) >= 0).nonzero(as_tuple=True)  # window order, then slot order
-        n = min(total, kept)
-        assert torch.equal(self.row_src[:n].cpu().long(), torch.stack([w, w * c.nq + s], 1)[:n])
-        assert torch.equal(self.row_meta[:n].cpu().view(torch.int32), c.qmeta[w, s][:n].view(torch.int32))
+        assert c.nq <= 256
+        np_ = lambda t: t.cpu().numpy()  # noqa: E731
+        check_plan_order(np_(c.nq_valid), c.nw, c.nq, np_(c.qmeta.contiguous().view(torch.int32)), self.row_cap, np_(self.perm),
+                         int(self.n_act.item()), np_(self.q_off), int(self.n_rows.item()), np_(self.row_src),
+                         np_(self.row_meta.view(torch.int32)))
 
     def blobs(self):
         from mssvt_amd import _lib
