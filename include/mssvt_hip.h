@@ -816,6 +816,51 @@ int mssvt_center_decode(int batch_size, int num_classes, int H, int W, int num_v
                         float score_thresh, void *workspace, float *cand_boxes, float *cand_scores, int *cand_labels,
                         int *cand_num, void *stream);
 
+/* CenterHead's training loss of ONE head for the whole batch, forward and backward (ref: CenterHead.get_loss,
+ * pcdet/models/dense_heads/center_head.py:220-250, with FocalLossCenterNet / RegLossCenterNet,
+ * pcdet/utils/loss_utils.py:264-386); no host synchronisation, nothing read back, no float atomics: every sum has a fixed
+ * order, so results are bit-identical run to run and across streams.
+ * hm (B, C, H, W) f32 RAW logits, heatmap (B, C, H, W) f32 targets; the regression maps in HEAD_ORDER as up to six separate
+ * contiguous (B, ch_k, H, W) f32 tensors (NULL / 0 for unused ones; they are never concatenated): code_size D = sum ch_k,
+ * code dimension d indexes their channels in order; target_boxes (B, M, target_stride >= D) f32, columns 0..D-1 used;
+ * inds, masks (B, M) i64 (masks 0 / 1); code_weights (D) f32 on the device.
+ *   p = clamp(sigmoid(x), (float)1e-4, (float)(1 - 1e-4));   pos = sum_{gt == 1} log(p) (1 - p)^2;
+ *   neg = sum_{gt < 1} log(1 - p) p^2 (1 - gt)^4;   num_pos = #{gt == 1};
+ *   hm_loss = -(pos + neg) / num_pos if num_pos > 0 else -neg  (decided on the device);   num = #{masks != 0};
+ *   per_dim[d] = sum_{b,j unmasked} |map_d[b, :, inds[b,j]] - target_boxes[b,j,d]| / max(num, 1);
+ *   loc_loss = loc_weight * sum_d code_weights[d] per_dim[d].
+ * A masked-out slot is not read (its index and target row may hold anything); an unmasked slot whose index lies outside
+ * [0, H W) counts in num and contributes neither loss nor gradient.  Sums are double from the first add, rounded once.
+ * forward: two launches.  workspace: mssvt_center_loss_workspace_bytes(...) bytes (0: shape refused), 8-byte aligned, no
+ * need to clear it.  out (4 + D floats, kept for the backward): [0] hm_loss, [1] loc_loss, [2] num_pos and [3] num as int32
+ * bit patterns, [4 + d] per_dim[d].
+ * backward: at most three launches.  g_hm / g_loc: the upstream gradients of hm_loss / loc_loss as DEVICE scalars (NULL:
+ * zero).  d_hm (B, C, H, W) or NULL: every element written once (through the clamp as torch does: zero where the sigmoid
+ * lies outside the bounds); recomputed from hm and heatmap, the forward saves no gradient buffer.  d_map_k (B, ch_k, H, W)
+ * or NULL (no gradient wanted): zero-filled by the call, then the cell of slot (b, j) gets g_loc loc_weight
+ * code_weights[d] sign(pred - target) / max(num, 1) (sign(0) = 0), slots that share a cell summed in ascending j.
+ * The heat-map passes run a grid that depends on n = B C H W alone: min(ceil(n / MSSVT_CENTER_LOSS_SWEEP),
+ * MSSVT_CENTER_LOSS_MAX_BLOCKS) workgroups.  Limits: M <= MSSVT_CENTER_LOSS_MAX_OBJS, D <= MSSVT_CENTER_LOSS_MAX_CODE,
+ * n < 2^31, B M < 2^31; MSSVT_E_TOOLARGE beyond.  Null pointers and non-positive sizes: MSSVT_E_BADARG before any HIP call. */
+#define MSSVT_CENTER_LOSS_SWEEP 1024
+#define MSSVT_CENTER_LOSS_MAX_BLOCKS 2048
+#define MSSVT_CENTER_LOSS_MAX_OBJS 4096
+#define MSSVT_CENTER_LOSS_MAX_CODE 16
+long long mssvt_center_loss_workspace_bytes(int batch_size, int num_classes, int H, int W, int num_max_objs, int code_size);
+int mssvt_center_loss_forward(int batch_size, int num_classes, int H, int W, int num_max_objs, int code_size,
+                              int target_stride, const float *hm, const float *heatmap, const float *map0, int ch0,
+                              const float *map1, int ch1, const float *map2, int ch2, const float *map3, int ch3,
+                              const float *map4, int ch4, const float *map5, int ch5, const float *target_boxes,
+                              const long long *inds, const long long *masks, const float *code_weights, float loc_weight,
+                              void *workspace, float *out, void *stream);
+int mssvt_center_loss_backward(int batch_size, int num_classes, int H, int W, int num_max_objs, int code_size,
+                               int target_stride, const float *hm, const float *heatmap, const float *map0, int ch0,
+                               const float *map1, int ch1, const float *map2, int ch2, const float *map3, int ch3,
+                               const float *map4, int ch4, const float *map5, int ch5, const float *target_boxes,
+                               const long long *inds, const long long *masks, const float *code_weights, float loc_weight,
+                               const float *out, const float *g_hm, const float *g_loc, float *d_hm, float *d_map0,
+                               float *d_map1, float *d_map2, float *d_map3, float *d_map4, float *d_map5, void *stream);
+
 /* The NMS of mssvt_nms_bev / mssvt_nms_normal (`normal` != 0) for a batch of padded candidate lists whose lengths live on
  * the device (the outputs of mssvt_center_decode): two launches whose sizes depend on K and pre_max only, nothing read back.
  * Per sample b: n = min(cand_num[b], pre_max) rows of cand_boxes[b] (K rows of row_floats >= 7 floats, descending score);

@@ -231,6 +231,111 @@ def centernet_reg_loss(maps, mask, ind, target):
     return per_dim / torch.clamp_min(num, 1.0)
 
 
+CENTER_LOSS_SWEEP = 1024  # include/mssvt_hip.h MSSVT_CENTER_LOSS_SWEEP: elements per workgroup and grid-stride step
+CENTER_LOSS_MAX_BLOCKS = 2048  # MSSVT_CENTER_LOSS_MAX_BLOCKS
+CENTER_LOSS_MAX_OBJS = 4096  # MSSVT_CENTER_LOSS_MAX_OBJS
+CENTER_LOSS_MAX_CODE = 16  # MSSVT_CENTER_LOSS_MAX_CODE
+CENTER_LOSS_MAX_MAPS = 6
+
+
+def _map_args(maps):
+    """Six (pointer, channels) pairs: the maps, then NULL / 0."""
+    pairs = [(_lib.ptr(t), int(t.shape[1])) for t in maps] + [(None, 0)] * (CENTER_LOSS_MAX_MAPS - len(maps))
+    return [v for pair in pairs for v in pair]
+
+
+class _CenterLoss(torch.autograd.Function):
+    """csrc/center_loss.hip under autograd: float32 contiguous device tensors only (``center_loss`` converts)."""
+
+    @staticmethod
+    def forward(ctx, hm, heatmap, target_boxes, inds, masks, code_weights, loc_weight, *reg_maps):
+        B, C, H, W = (int(v) for v in hm.shape)
+        M, DT = int(target_boxes.shape[1]), int(target_boxes.shape[2])
+        D = sum(int(t.shape[1]) for t in reg_maps)
+        nbytes = int(_lib.lib().mssvt_center_loss_workspace_bytes(B, C, H, W, M, D))
+        if nbytes <= 0:
+            raise _lib.MssvtHipError("center_loss: shape beyond the kernel's limits (M <= %d, D <= %d, B C H W < 2^31): "
+                                     "B=%d C=%d H=%d W=%d M=%d D=%d" % (CENTER_LOSS_MAX_OBJS, CENTER_LOSS_MAX_CODE, B, C, H, W, M, D))
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=hm.device)  # fully written before it is read
+        out = torch.empty(4 + D, dtype=torch.float32, device=hm.device)
+        m = _map_args(reg_maps)
+        _lib.call("mssvt_center_loss_forward", B, C, H, W, M, D, DT, hm.data_ptr(), _lib.ptr(heatmap), m[0], m[1], m[2], m[3],
+                  m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11], _lib.ptr(target_boxes), _lib.ptr(inds), _lib.ptr(masks),
+                  _lib.ptr(code_weights), float(loc_weight), ws.data_ptr(), out.data_ptr(), _lib.stream())
+        ctx.save_for_backward(hm, heatmap, target_boxes, inds, masks, code_weights, out, *reg_maps)
+        ctx.loc_weight = float(loc_weight)
+        ctx.set_materialize_grads(False)  # an absent upstream gradient stays None: NULL, no zero tensor is built
+        hm_loss, loc_loss, per_dim = out[0], out[1], out[4:4 + D]
+        ctx.mark_non_differentiable(per_dim)
+        return hm_loss, loc_loss, per_dim
+
+    @staticmethod
+    def backward(ctx, g_hm, g_loc, _g_per_dim):
+        hm, heatmap, target_boxes, inds, masks, code_weights, out = ctx.saved_tensors[:7]
+        reg_maps = ctx.saved_tensors[7:]
+        B, C, H, W = (int(v) for v in hm.shape)
+        M, DT = int(target_boxes.shape[1]), int(target_boxes.shape[2])
+        D = sum(int(t.shape[1]) for t in reg_maps)
+        # an absent upstream gradient is zero (NULL); a present one is a float32 device scalar
+        g_hm = None if g_hm is None else g_hm.float().contiguous()
+        g_loc = None if g_loc is None else g_loc.float().contiguous()
+        d_hm = None
+        if ctx.needs_input_grad[0]:  # on hm's 16-byte phase, so that the pass keeps its 16-byte stores
+            phase = (hm.data_ptr() % 16) // 4
+            d_hm = torch.empty(hm.numel() + 3, dtype=torch.float32, device=hm.device)[phase:phase + hm.numel()].view(hm.shape)
+        d_maps = [torch.empty_like(t) if ctx.needs_input_grad[7 + k] else None for k, t in enumerate(reg_maps)]
+        m = _map_args(reg_maps)
+        dm = [_lib.ptr(t) for t in d_maps] + [None] * (CENTER_LOSS_MAX_MAPS - len(d_maps))
+        _lib.call("mssvt_center_loss_backward", B, C, H, W, M, D, DT, hm.data_ptr(), _lib.ptr(heatmap), m[0], m[1], m[2],
+                  m[3], m[4], m[5], m[6], m[7], m[8], m[9], m[10], m[11], _lib.ptr(target_boxes), _lib.ptr(inds),
+                  _lib.ptr(masks), _lib.ptr(code_weights), ctx.loc_weight, out.data_ptr(), _lib.ptr(g_hm), _lib.ptr(g_loc),
+                  _lib.ptr(d_hm), dm[0], dm[1], dm[2], dm[3], dm[4], dm[5], _lib.stream())
+        return (d_hm, None, None, None, None, None, None) + tuple(d_maps)
+
+
+def center_loss(hm, reg_maps, heatmap, target_boxes, inds, masks, code_weights, loc_weight):
+    """The loss of ONE head on the device (csrc/center_loss.hip): ``centernet_focal_loss`` of the clamped sigmoid of the
+    RAW logits hm (B, C, H, W) against heatmap, and loc_weight x sum(code_weights x ``centernet_reg_loss``) of the
+    regression maps -- a list of (B, c_k, H, W) tensors in HEAD_ORDER, never concatenated -- at inds / masks (B, M) against
+    target_boxes (B, M, D') whose first D = sum(c_k) columns are used.  Returns (hm_loss, loc_loss, per_dim): 0-d, 0-d and
+    (D) float32 on the device; differentiable in hm and in every map (two launches forward, at most three backward, no float
+    atomics: bit-identical run to run), per_dim detached.  Nothing is read back: the ``num_pos == 0`` branch is taken on
+    the device.  A masked-out slot is not read; an unmasked slot whose index lies outside the map counts in the number of
+    objects and gives neither loss nor gradient.  Other float dtypes are converted here, under autograd.  code_weights: D
+    numbers or a device tensor (a list costs a host-to-device copy: ``CenterHead`` keeps the tensor)."""
+    reg_maps = list(reg_maps)
+    if not (hm.is_cuda and hm.dim() == 4 and all(t.is_cuda and t.dim() == 4 for t in reg_maps)):
+        raise _lib.MssvtHipError("center_loss needs (B, C, H, W) maps on the GPU (no CPU path)")
+    if not (heatmap.is_cuda and target_boxes.is_cuda and inds.is_cuda and masks.is_cuda):
+        raise _lib.MssvtHipError("center_loss needs its targets on the GPU (no CPU path)")
+    if len(reg_maps) > CENTER_LOSS_MAX_MAPS:
+        raise _lib.MssvtHipError("center_loss: %d regression maps, the kernel takes %d" % (len(reg_maps), CENTER_LOSS_MAX_MAPS))
+    B, C, H, W = (int(v) for v in hm.shape)
+    D = sum(int(t.shape[1]) for t in reg_maps)
+    dev = hm.device
+    for t in reg_maps:
+        if (int(t.shape[0]), int(t.shape[2]), int(t.shape[3])) != (B, H, W) or t.device != dev:
+            raise _lib.MssvtHipError("center_loss: a regression map is not (%d, c, %d, %d) on the heat map's device" % (B, H, W))
+    if tuple(heatmap.shape) != (B, C, H, W) or target_boxes.dim() != 3 or int(target_boxes.shape[0]) != B or \
+            tuple(inds.shape) != tuple(target_boxes.shape[:2]) or tuple(masks.shape) != tuple(inds.shape):
+        raise _lib.MssvtHipError("center_loss: heatmap must be %s, target_boxes (B, M, D'), inds / masks (B, M)" % ((B, C, H, W),))
+    M, DT = int(target_boxes.shape[1]), int(target_boxes.shape[2])
+    if DT < D:
+        raise _lib.MssvtHipError("center_loss: target_boxes has %d columns, the maps have %d channels" % (DT, D))
+    if min(B, C, H, W, M) == 0 or D == 0:
+        raise _lib.MssvtHipError("center_loss: empty shape B=%d C=%d H=%d W=%d M=%d D=%d (CenterHead.get_loss keeps the torch "
+                                 "expressions for these)" % (B, C, H, W, M, D))
+    if not torch.is_tensor(code_weights):
+        code_weights = torch.tensor([float(v) for v in code_weights], dtype=torch.float32, device=dev)
+    code_weights = code_weights.detach().to(device=dev, dtype=torch.float32).contiguous()
+    if code_weights.numel() != D:
+        raise _lib.MssvtHipError("center_loss: %d code weights for %d code dimensions" % (code_weights.numel(), D))
+    return _CenterLoss.apply(hm.float().contiguous(), heatmap.detach().float().contiguous(),
+                             target_boxes.detach().float().contiguous(), inds.detach().long().contiguous(),
+                             masks.detach().long().contiguous(), code_weights, float(loc_weight),
+                             *[t.float().contiguous() for t in reg_maps])
+
+
 class CenterHead(nn.Module):
     def __init__(self, model_cfg, input_channels, num_class, class_names, grid_size, point_cloud_range, voxel_size,
                  predict_boxes_when_training=True):
@@ -263,6 +368,8 @@ class CenterHead(nn.Module):
         self._label_tables_dev = {}  # device -> label_tables() as an int32 tensor (heads, C + 1)
         self._class_maps_dev = {}  # device -> _class_maps on that device (generate_predicted_boxes_padded)
         self.padded_predictions = False  # eval forward: final_box_padded (no host sync) instead of final_box_dicts
+        self.fused_loss = False  # get_loss on the GPU: center_loss per head, tb_dict as device tensors (no host sync)
+        self._code_weights_dev = {}  # device -> LOSS_WEIGHTS.code_weights as a float32 tensor (get_loss with fused_loss)
 
     def label_tables(self):
         """int array [label 0..C][head]: the class inside the head that a box of that label gets, or -1 when the head
@@ -462,8 +569,43 @@ class CenterHead(nn.Module):
                 out[key].append(torch.stack([t[j] for t in per_sample], dim=0).to(gt_boxes.device))
         return out
 
+    def _code_weights_on(self, device):
+        t = self._code_weights_dev.get(device)
+        if t is None:
+            weights = _get(_get(self.model_cfg, "LOSS_CONFIG"), "LOSS_WEIGHTS")
+            t = torch.tensor([float(v) for v in weights["code_weights"]], dtype=torch.float32, device=device)
+            self._code_weights_dev[device] = t
+        return t
+
+    def get_loss_fused(self):
+        """``get_loss`` with ``center_loss`` per head (csrc/center_loss.hip): two launches forward and at most three
+        backward per head, and no host synchronisation -- the loss terms of tb_dict are detached 0-d device tensors, read
+        them back when they are logged.  A head without object slots or with an empty map keeps the torch expressions."""
+        weights = _get(_get(self.model_cfg, "LOSS_CONFIG"), "LOSS_WEIGHTS")
+        order = list(_get(self.separate_head_cfg, "HEAD_ORDER"))
+        td = self.forward_ret_dict["target_dicts"]
+        loss, tb = 0, {}
+        for idx, pd in enumerate(self.forward_ret_dict["pred_dicts"]):
+            if td["inds"][idx].numel() == 0 or pd["hm"].numel() == 0:
+                hm = torch.clamp(pd["hm"].sigmoid(), min=1e-4, max=1 - 1e-4)
+                hm_loss = centernet_focal_loss(hm, td["heatmaps"][idx])
+                reg = centernet_reg_loss(torch.cat([pd[name] for name in order], dim=1), td["masks"][idx], td["inds"][idx],
+                                         td["target_boxes"][idx])
+                loc_loss = (reg * reg.new_tensor(list(weights["code_weights"]))).sum() * weights["loc_weight"]
+            else:
+                hm_loss, loc_loss, _ = center_loss(pd["hm"], [pd[name] for name in order], td["heatmaps"][idx],
+                                                   td["target_boxes"][idx], td["inds"][idx], td["masks"][idx],
+                                                   self._code_weights_on(pd["hm"].device), weights["loc_weight"])
+            loss = loss + hm_loss + loc_loss
+            tb["hm_loss_head_%d" % idx] = hm_loss.detach()
+            tb["loc_loss_head_%d" % idx] = loc_loss.detach()
+        tb["rpn_loss"] = loss.detach()
+        return loss, tb
+
     def get_loss(self):
         """ref :220-250: per head the focal loss of the clamped sigmoid heat map + loc_weight x sum(code_weights x L1)."""
+        if self.fused_loss and self.forward_ret_dict["pred_dicts"][0]["hm"].is_cuda:
+            return self.get_loss_fused()
         weights = _get(_get(self.model_cfg, "LOSS_CONFIG"), "LOSS_WEIGHTS")
         order = list(_get(self.separate_head_cfg, "HEAD_ORDER"))
         loss, tb = 0, {}

@@ -118,6 +118,8 @@ class CenterPoint(nn.Module):
             batch_dict = m(batch_dict)
         if self.training:  # ref centerpoint.py:13-32: ({'loss': ...}, tb_dict, disp_dict)
             loss, tb_dict = self.dense_head.get_loss()
+            if getattr(self.dense_head, "fused_loss", False):  # the loss stays on the device: no host synchronisation
+                return dict(loss=loss), dict(loss_rpn=loss.detach(), **tb_dict), {}
             return dict(loss=loss), dict(loss_rpn=loss.item(), **tb_dict), {}
         return self.post_processing(batch_dict)
 
