@@ -497,21 +497,29 @@ __global__ void __launch_bounds__(MSSVT_WAVE) k_attn_pack(const float *Wq, const
     dst[64] = lo;
 }
 
-// straight copy of n16 16-byte pieces into the LDS, every load of a thread in flight before its first store
+// straight copy of n16 16-byte pieces into the LDS, every load of a thread in flight before its first store (in two
+// halves, so that a caller can put loads of its own between them: k_attn_kvh)
 template <int N16, int THREADS>
-__device__ __forceinline__ void attn_stage16(float4 *lds, const float4 *src) {
-    constexpr int PER = (N16 + THREADS - 1) / THREADS;
-    float4 v[PER];
+__device__ __forceinline__ void attn_stage16_load(float4 (&v)[(N16 + THREADS - 1) / THREADS], const float4 *src) {
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
+    for (int k = 0; k < (N16 + THREADS - 1) / THREADS; ++k) {
         const int e = threadIdx.x + k * THREADS;
         if (N16 % THREADS == 0 || e < N16) v[k] = src[e];
     }
+}
+template <int N16, int THREADS>
+__device__ __forceinline__ void attn_stage16_store(float4 *lds, const float4 (&v)[(N16 + THREADS - 1) / THREADS]) {
 #pragma unroll
-    for (int k = 0; k < PER; ++k) {
+    for (int k = 0; k < (N16 + THREADS - 1) / THREADS; ++k) {
         const int e = threadIdx.x + k * THREADS;
         if (N16 % THREADS == 0 || e < N16) lds[e] = v[k];
     }
+}
+template <int N16, int THREADS>
+__device__ __forceinline__ void attn_stage16(float4 *lds, const float4 *src) {
+    float4 v[(N16 + THREADS - 1) / THREADS];
+    attn_stage16_load<N16, THREADS>(v, src);
+    attn_stage16_store<N16, THREADS>(lds, v);
 }
 
 // ---- A, kv16 form: rows -> Qt.  OUT 0: Qt in fp32 for k_attn_kv; 1: Qt as (hi, lo) fragments for k_attn_kvh<.., false>;
@@ -1025,8 +1033,8 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, 2) k_attn_kv(AttnP
 //             order and the Xbar store undoes the permutation in its address;
 //   keys:     k slot (g, j) of step s <-> key 32 s + 16 (j / 4) + 4 g + j % 4 = the accumulator layout of two score tiles,
 //             so the normalised scores are the B operand of the second product as they stand.
-// LDS image per wave: [hi | lo][key][channel] fp16, rows of 2 CG + 16 bytes (36 KiB per workgroup at K = 32: four
-// workgroups = 4 waves / SIMD per CU; the 8 rows a 32-lane half of a transposed read touches start 36 banks apart).  Unused key tiles hold zeros (their P is 0, but the product needs finite
+// LDS image per wave: [hi | lo][key][channel] fp16, rows of 2 CG + 16 bytes (36 KiB per workgroup at K = 32: three
+// workgroups = 3 waves / SIMD per CU, the 170 registers that two pass bodies and the prefetched window need; the 8 rows a 32-lane half of a transposed read touches start 36 banks apart).  Unused key tiles that a pass body reads hold zeros (their P is 0, but the product needs finite
 // operands).  The caller guarantees the fp16 range of tokens and Qt (fused._attn_kv16_ok).
 #define KVH_RS(cg) (2 * (cg) + 16)  // bytes per image row: 16-byte aligned, 36 banks at Cg = 64 (transposed reads: one 2-way pair per half)
 __device__ __forceinline__ h16x4 lds_read_tr16(const char *p) {
@@ -1037,11 +1045,11 @@ __device__ __forceinline__ h16x4 lds_read_tr16(const char *p) {
 // Wk fragments of the pack blob staged into the LDS: one product per head with the columns of the other heads zeroed in
 // the B operand, all accumulated into one tile -- NH x NT x 3 K = 16 instructions for 1 instead of 4 row loads per lane
 template <int CG, int HD, int HP, int KT, bool QP>
-__global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 : 4) : 2) k_attn_kvh(AttnPack pack) {
+__global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || CG >= 64 ? 3 : 4) : 2) k_attn_kvh(AttnPack pack) {
     static_assert(!QP || (HD == 16 && (CG / HD) % 2 == 0), "Q' hand-off: head = one 16-row tile, heads in pairs");
     static_assert(CG % 32 == 0 && KT % 2 == 0, "32-channel and 32-key steps");
     const AttnArgs &a = pack.g[blockIdx.y];
-    constexpr int NT = CG / 16, NP = CG / 32, NS = KT / 2, NH = CG / HD, QROW = HP * CG, QPP = 16 / HP;
+    constexpr int NT = CG / 16, NP = CG / 32, NH = CG / HD, QROW = HP * CG, QPP = 16 / HP;
     constexpr int RS = KVH_RS(CG), IMG = KT * 16 * RS;  // bytes: image row, one (hi or lo) image
     extern __shared__ float4 lds4[];
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
@@ -1050,11 +1058,21 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
     constexpr int WKB = QP ? AttnBlob<CG>::WV2 - AttnBlob<CG>::WK2 : 0;
     char *Ti = reinterpret_cast<char *>(lds4) + WKB + (size_t)wv * 2 * IMG;
     const h16x8 *WkF2 = reinterpret_cast<const h16x8 *>(lds4);
-    if (QP) {  // before any wave can leave: every wave of the workgroup meets at the barrier
-        attn_stage16<(WKB > 0 ? WKB : 16) / 16, ATTN_ROW_WAVES * MSSVT_WAVE>(
-            lds4, reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.packed) + AttnBlob<CG>::WK2));
-        __syncthreads();
-    }
+    // A zero the compiler cannot see through.  A word loaded at a wave-uniform address is otherwise fetched through the scalar
+    // cache, or copied to a scalar register right behind its vector load -- either way with a wait at the place of the
+    // load.  With `vz` in its byte offset the word is an ordinary vector load: it returns in issue order with the loads around
+    // it and is waited for where readfirstlane uses it.
+    unsigned vz = 0;
+    asm volatile("" : "+v"(vz));
+#define KVH_WORD(ptr_, idx_) \
+    (*reinterpret_cast<const int *>(reinterpret_cast<const char *>(ptr_) + ((unsigned)(idx_) * 4u + vz)))
+    // Prologue: four dependent round trips -- window count, work order, metadata, rows -- with the Wk staging in flight
+    // under the first two (it was five: staging + barrier in front of the same four).  The count is asked for FIRST, as
+    // a vector load, and the staging pieces leave behind it before it is waited for; the wave's first three work-order
+    // entries leave as soon as the count is there and travel during the LDS stores and the barrier.  (Reading the order
+    // ahead of the count would save one more trip, but the entry points carry no window capacity, so no index of `perm`
+    // at or beyond *num_wins can be bounded by its allocation.)
+    const int n_act_v = KVH_WORD(a.num_wins, 0);
     // positional MLP operand of this lane: A row la of tile u <-> channel (16 * u + la), input g: the weight of the
     // relative offset (g < 3) | bias + window-centre part (g = 3: summed over the three lanes that hold its weights)
     float wrel[NT], wctr[NT];
@@ -1062,42 +1080,75 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
     for (int u = 0; u < NT; ++u) {
         const int c = (16 * u + la);
         const float *wp = a.Wp + (size_t)(a.c0 + c) * 6;
-        wrel[u] = g < 3 ? wp[g] : a.bp[a.c0 + c];
-        wctr[u] = g < 3 ? wp[3 + g] : 0.f;
+        const float w_rel = wp[min(g, 2)], w_ctr = wp[3 + min(g, 2)], b_ = a.bp[a.c0 + c];  // (no lane-dependent branch)
+        wrel[u] = g < 3 ? w_rel : b_;
+        wctr[u] = g < 3 ? w_ctr : 0.f;
     }
-    const int n_act = __builtin_amdgcn_readfirstlane(*a.num_wins);
+    constexpr int WK16 = (WKB > 0 ? WKB : 16) / 16;
+    float4 wk_v[(WK16 + ATTN_ROW_WAVES * MSSVT_WAVE - 1) / (ATTN_ROW_WAVES * MSSVT_WAVE)];
+    if (QP)
+        attn_stage16_load<WK16, ATTN_ROW_WAVES * MSSVT_WAVE>(
+            wk_v, reinterpret_cast<const float4 *>(reinterpret_cast<const char *>(a.packed) + AttnBlob<CG>::WK2));
+    const int n_act = __builtin_amdgcn_readfirstlane(n_act_v);
     const int wstep = gridDim.x * ATTN_ROW_WAVES;
     const int K = a.K;
     int wi = __builtin_amdgcn_readfirstlane(blockIdx.x * ATTN_ROW_WAVES + wv);
+    const int w_last = n_act - 1;
+    // the wave's first three windows, loaded without a branch: indices <= w_last, inside the *num_wins entries that
+    // mssvt_plan_order wrote; with no active window at all the three loads read the count word again instead
+    const int *perm0 = n_act > 0 ? a.perm : a.num_wins;
+    const int w_p0 = KVH_WORD(perm0, max(min(wi, w_last), 0));
+    const int w_p1 = KVH_WORD(perm0, max(min(wi + wstep, w_last), 0));
+    const int w_p2 = KVH_WORD(perm0, max(min(wi + 2 * wstep, w_last), 0));
+    if (QP) {  // before any wave can leave: every wave of the workgroup meets at the barrier
+        attn_stage16_store<WK16, ATTN_ROW_WAVES * MSSVT_WAVE>(lds4, wk_v);
+        __syncthreads();
+    }
     if (wi >= n_act) return;
     const __amdgpu_buffer_rsrc_t xr_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(a.xhat), 0, -1, 0x00020000);
     const __amdgpu_buffer_rsrc_t km_rs = __builtin_amdgcn_make_buffer_rsrc(const_cast<float4 *>(a.kmeta), 0, -1, 0x00020000);
     const unsigned row_bytes = (unsigned)a.C * 4u, lane_off = ((unsigned)a.c0 + 4u * g) * 4u;
     // piece S of a row: channels 16 S + 4 g + i (dense: the four g lanes of a key read 64 contiguous bytes)
 #define KVH_ROW4(off_, S_) __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(xr_rs, (off_) + 64u * (S_), 0, 0))
-    // the software pipeline of k_attn_kv: window ids three steps ahead, metadata two, raw rows one; every load unconditional
+    // the software pipeline of k_attn_kv: window ids three steps ahead, metadata two, raw rows one; every load unconditional.
+    // The window id and the two counts are wave-uniform words that the NEXT iteration consumes.  Left to the compiler they
+    // cross the loop edge in scalar registers, and the copy out of the loaded vector register -- with the wait for every
+    // load issued before it, the next window's rows among them -- lands right behind the load: one full round trip per
+    // window, the pipeline undone.  Their byte offsets therefore carry a zero the compiler cannot see through (`vz`): the
+    // words stay in vector registers until readfirstlane at the point of use, one iteration later.
     int w_p;
     float4 wc_m, km_m[KT];
     int nqv_m, qbase_m;
 #define KVH_LOAD_META()                                                                    \
     {                                                                                      \
-        wc_m = a.wcentre[w_p];                                                             \
-        nqv_m = a.nq_valid[w_p];                                                           \
-        qbase_m = a.q_off[w_p];                                                            \
+        const int w_ = __builtin_amdgcn_readfirstlane(w_p);                                \
+        wc_m = a.wcentre[w_];                                                              \
+        nqv_m = KVH_WORD(a.nq_valid, w_);                                                  \
+        qbase_m = KVH_WORD(a.q_off, w_);                                                   \
         _Pragma("unroll") for (int t = 0; t < KT; ++t)                                     \
             km_m[t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(    \
-                km_rs, ((unsigned)w_p * (unsigned)K + (unsigned)min(16 * t + la, K - 1)) * 16u, 0, 0)); \
+                km_rs, ((unsigned)w_ * (unsigned)K + (unsigned)min(16 * t + la, K - 1)) * 16u, 0, 0)); \
     }
     float4 wc_r;
     int nqv_r, qbase_r;
     float rel_r[KT];
     unsigned vmask_r, used_r;
     f32x4 T1n[KT][NT];
-    // (round 6 measured the first pass's Q' piece travelling with the rows, one window ahead -- the load that cost the CEILING
-    // kernel 6 us per odd launch -- in this kernel: 52.1 / 26.0 against 51.4 / 25.6 us, no gain: three waves per SIMD hide it)
+    // The first pass's Q' piece travels with the rows, one window ahead: loaded where it is used it is the youngest load
+    // in flight, and the wait for it drains the next window's rows.  (Round 6 measured this alone and saw no gain, 52.1 /
+    // 26.0 against 51.4 / 25.6 us: the scalar copies above drained the queue all the same.)
+    h16x8 qp8_n = h16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    const int hh = la % HP;
+    const bool head_ok = hh < NH;
 #define KVH_ISSUE_ROWS()                                                                   \
     {                                                                                      \
-        wc_r = wc_m; nqv_r = nqv_m; qbase_r = qbase_m;                                     \
+        wc_r = wc_m;                                                                       \
+        nqv_r = __builtin_amdgcn_readfirstlane(nqv_m);                                     \
+        qbase_r = __builtin_amdgcn_readfirstlane(qbase_m);                                 \
+        if (QP) {                                                                          \
+            const int nq_ = qbase_r + nqv_r <= a.row_capacity ? nqv_r : 0;                 \
+            qp8_n = reinterpret_cast<const h16x8 *>(a.qbuf + ((size_t)qbase_r + max(min(la / HP, nq_ - 1), 0)) * QROW)[(head_ok ? hh : 0) * 4 + g]; \
+        }                                                                                  \
         vmask_r = 0; used_r = 0;                                                           \
         _Pragma("unroll") for (int t = 0; t < KT; ++t) {                                   \
             const int r_ = __builtin_bit_cast(int, km_m[t].w);                             \
@@ -1110,15 +1161,12 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
             _Pragma("unroll") for (int S = 0; S < NT; ++S) T1n[t][S] = KVH_ROW4(ro_, S);   \
         }                                                                                  \
     }
-    const int w_last = n_act - 1;
-    w_p = a.perm[wi];
+    w_p = w_p0;
     KVH_LOAD_META()
-    w_p = a.perm[min(wi + wstep, w_last)];
-    const int hh = la % HP;
-    const bool head_ok = hh < NH;
+    w_p = w_p1;
     KVH_ISSUE_ROWS()
     KVH_LOAD_META()
-    w_p = a.perm[min(wi + 2 * wstep, w_last)];
+    w_p = w_p2;
     // transposed reads: lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of its 4 x 16 block
     const char *tr_base = Ti + (4 * g + (la >> 2)) * RS + 8 * (la & 3);
     for (; wi < n_act; wi += wstep) {
@@ -1126,9 +1174,11 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
         const int nqv = qbase_r + nqv_r <= a.row_capacity ? nqv_r : 0;
         const size_t qbase = (size_t)qbase_r;
         const unsigned vmask = vmask_r, used = used_r;
+        // every live key in the first half of the list (wave-uniform): KT = 2 -- in tile 0; KT = 4 -- in its first 32-key step
+        const bool front = (used >> (KT / 2)) == 0u;
         const float ctrb = lane_pick4(g, wc.x, wc.y, wc.z, wc.z);  // wctr is 0 for g = 3
         // key tokens = row + relu(positional MLP), split once, straight into the image (both products read it: the score
-        // product row-wise, the second one transposed -- no token registers live across the passes: 4 waves / SIMD)
+        // product row-wise, the second one transposed -- no token registers live across the passes)
         float wu[NT];  // A operand of the positional product: once per window (the window centre), not once per key tile
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
@@ -1139,6 +1189,9 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
         }
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
+            // zeros only where a pass body reads them: a dead tile beside a live one in a 32-key step (none at KT = 2,
+            // where a dead tile 1 means the `front` body, which reads tile 0 alone)
+            if (!(used >> t & 1) && (KT == 2 || (front && t >= KT / 2))) continue;
 #pragma unroll
             for (int P = 0; P < NP; ++P) {
                 h16x8 th = h16x8{0, 0, 0, 0, 0, 0, 0, 0}, tl = th;
@@ -1160,10 +1213,8 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
             }
         }
         h16x8 qh[NP], ql[NP];
-        h16x8 qp8 = h16x8{0, 0, 0, 0, 0, 0, 0, 0};  // Q' mode: (hi x 4 | lo x 4) of this lane's column
-        if (QP) {
-            qp8 = reinterpret_cast<const h16x8 *>(a.qbuf + (qbase + max(min(la / HP, nqv - 1), 0)) * QROW)[(head_ok ? hh : 0) * 4 + g];
-        } else {
+        h16x8 qp8 = qp8_n;  // Q' mode: (hi x 4 | lo x 4) of this lane's column
+        if (!QP) {
             const h16x8 *qr_ = reinterpret_cast<const h16x8 *>(a.qbuf + (qbase + max(min(la / HP, nqv - 1), 0)) * QROW + (head_ok ? hh : 0) * CG);
 #pragma unroll
             for (int P = 0; P < NP; ++P) {
@@ -1173,120 +1224,143 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP ? 3 
         }
         KVH_ISSUE_ROWS()
         KVH_LOAD_META()
-        w_p = a.perm[min(wi + 3 * wstep, w_last)];
+        w_p = KVH_WORD(a.perm, min(wi + 3 * wstep, w_last));
         wave_lds_sync();
-        for (int q0 = 0; q0 < nqv; q0 += QPP) {
-            const int q = q0 + la / HP;
-            const bool q_ok = q < nqv && head_ok;
-            float *xrow = a.qbuf + (qbase + min(q, nqv - 1)) * QROW + (head_ok ? hh : 0) * CG;
-            if (q0 > 0) {
+        // One pass body per set of live 32-key steps, chosen ONCE per window (`front` is known before its passes start), so
+        // that a pass is straight-line code: FRONT -- every live key in the first half of the list.  KT = 2: tile 0 alone
+        // (9.6 of 32 slots are live on the flagship frame): the softmax runs over its 4 values per lane, and the second
+        // product takes tile 1's half of both operands as zero registers -- the same K = 32 instruction on the same operand
+        // values as with zeros read back from the image and P = exp2(-inf) = +0, and the softmax loses only exact +0 terms
+        // and -inf candidates: the bits of the two-tile body.  KT = 4: the second step is left out whole (its products
+        // are +0 added to sums that are never -0); tiles are not told apart inside a step.
+        const auto passes = [&](auto front_c) __attribute__((always_inline)) {
+            constexpr int LT = decltype(front_c)::value ? KT / 2 : KT, LS = (LT + 1) / 2;  // tiles, 32-key steps this body reads
+            for (int q0 = 0; q0 < nqv; q0 += QPP) {
+                const int q = q0 + la / HP;
+                const bool q_ok = q < nqv && head_ok;
+                float *xrow = a.qbuf + (qbase + min(q, nqv - 1)) * QROW + (head_ok ? hh : 0) * CG;
+                if (q0 > 0) {
+                    if (QP) {
+                        qp8 = reinterpret_cast<const h16x8 *>(a.qbuf + (qbase + min(q, nqv - 1)) * QROW)[(head_ok ? hh : 0) * 4 + g];
+                    } else {
+                        const h16x8 *qrow = reinterpret_cast<const h16x8 *>(xrow);
+#pragma unroll
+                        for (int P = 0; P < NP; ++P) {
+                            qh[P] = qrow[(P * 4 + g) * 2];
+                            ql[P] = qrow[(P * 4 + g) * 2 + 1];
+                        }
+                    }
+                }
                 if (QP) {
-                    qp8 = reinterpret_cast<const h16x8 *>(a.qbuf + (qbase + min(q, nqv - 1)) * QROW)[(head_ok ? hh : 0) * 4 + g];
-                } else {
-                    const h16x8 *qrow = reinterpret_cast<const h16x8 *>(xrow);
+                    // Qt^T[c][col] = sum_h sum_{k < 16} (scale Wk)[16 h + k][c] Q'[q(col)][16 h + k] [h == head(col)]
+                    const h16x4 z4 = h16x4{0, 0, 0, 0};
+                    const h16x4 bh = h16x4{qp8[0], qp8[1], qp8[2], qp8[3]}, bl = h16x4{qp8[4], qp8[5], qp8[6], qp8[7]};
+                    __builtin_amdgcn_sched_barrier(0);  // (the scheduler would hoist all 32 fragment reads: 70 spilled registers)
 #pragma unroll
                     for (int P = 0; P < NP; ++P) {
-                        qh[P] = qrow[(P * 4 + g) * 2];
-                        ql[P] = qrow[(P * 4 + g) * 2 + 1];
-                    }
-                }
-            }
-            if (QP) {
-                // Qt^T[c][col] = sum_h sum_{k < 16} (scale Wk)[16 h + k][c] Q'[q(col)][16 h + k] [h == head(col)]
-                const h16x4 z4 = h16x4{0, 0, 0, 0};
-                const h16x4 bh = h16x4{qp8[0], qp8[1], qp8[2], qp8[3]}, bl = h16x4{qp8[4], qp8[5], qp8[6], qp8[7]};
-                __builtin_amdgcn_sched_barrier(0);  // (the scheduler would hoist all 32 fragment reads: 70 spilled registers)
+                        f32x4 qt[2];
 #pragma unroll
-                for (int P = 0; P < NP; ++P) {
-                    f32x4 qt[2];
+                        for (int e = 0; e < 2; ++e) {
+                            const int u = 2 * P + e;
+                            f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
 #pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int u = 2 * P + e;
-                        f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
+                            for (int pr = 0; pr < NH / 2; ++pr) {  // heads 2 pr | 2 pr + 1 in the two halves of the k slots
+                                const h16x8 wh = WkF2[((pr * NT + u) * 2) * 64 + lane], wl = WkF2[((pr * NT + u) * 2 + 1) * 64 + lane];
+                                const h16x8 sh = h16_cat(hh == 2 * pr ? bh : z4, hh == 2 * pr + 1 ? bh : z4),
+                                            sl = h16_cat(hh == 2 * pr ? bl : z4, hh == 2 * pr + 1 ? bl : z4);
+                                MFMA_H(mm, wh, sh);
+                                MFMA_H(cr, wh, sl);
+                                MFMA_H(cr, wl, sh);
+                            }
 #pragma unroll
-                        for (int pr = 0; pr < NH / 2; ++pr) {  // heads 2 pr | 2 pr + 1 in the two halves of the k slots
-                            const h16x8 wh = WkF2[((pr * NT + u) * 2) * 64 + lane], wl = WkF2[((pr * NT + u) * 2 + 1) * 64 + lane];
-                            const h16x8 sh = h16_cat(hh == 2 * pr ? bh : z4, hh == 2 * pr + 1 ? bh : z4),
-                                        sl = h16_cat(hh == 2 * pr ? bl : z4, hh == 2 * pr + 1 ? bl : z4);
-                            MFMA_H(mm, wh, sh);
-                            MFMA_H(cr, wh, sl);
-                            MFMA_H(cr, wl, sh);
+                            for (int i = 0; i < 4; ++i) qt[e][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
                         }
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) qt[e][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
+                        h16_split8(qt[0], qt[1], qh[P], ql[P]);
+                        __builtin_amdgcn_sched_barrier(0);
                     }
-                    h16_split8(qt[0], qt[1], qh[P], ql[P]);
-                    __builtin_amdgcn_sched_barrier(0);
+                }
+                // scores S[key][col] = sum_c T[key][c] Qt[col][c]
+                f32x4 sc[LT];
+#pragma unroll
+                for (int t = 0; t < LT; ++t) {
+                    sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    if (KT > 2 && !(used >> t & 1)) continue;  // (KT = 2: the body says which tiles are live)
+                    f32x4 mm = sc[t], cr = sc[t];
+#pragma unroll
+                    for (int P = 0; P < NP; ++P) {
+                        const char *src = Ti + (16 * t + la) * RS + 64 * P + 16 * g;
+                        const h16x8 th = *reinterpret_cast<const h16x8 *>(src), tl = *reinterpret_cast<const h16x8 *>(src + IMG);
+                        MFMA_H(mm, th, qh[P]);
+                        MFMA_H(cr, th, ql[P]);
+                        MFMA_H(cr, tl, qh[P]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sc[t][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
+                }
+                // softmax over the unmasked keys in base 2 (QP: log2 e is folded into the Wk fragments): masked slots score -inf
+                float mx = -INFINITY;
+#pragma unroll
+                for (int t = 0; t < LT; ++t)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float sv = QP ? sc[t][i] : sc[t][i] * 1.4426950408889634f;
+                        sc[t][i] = (vmask >> (4 * t + i) & 1) ? sv : -INFINITY;
+                        mx = fmaxf(mx, sc[t][i]);
+                    }
+                mx = fmaxf(mx, lane_xor16(mx));
+                mx = fmaxf(mx, lane_xor32(mx));
+                float sum = 0.f;
+#pragma unroll
+                for (int t = 0; t < LT; ++t)
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const float e = __builtin_amdgcn_exp2f(sc[t][i] - mx);  // slot 0 of a list is never masked: mx is finite
+                        sc[t][i] = e;
+                        sum += e;
+                    }
+                sum += lane_xor16(sum);
+                sum += lane_xor32(sum);
+                const float inv = __builtin_amdgcn_rcpf(sum);
+                // Xbar^T[c][col] = sum_key T[key][c] P[key][col]
+                const h16x4 z4 = h16x4{0, 0, 0, 0};
+                h16x8 ph[LS], pl[LS];
+                if constexpr (LT == 1) {  // the step's second tile: P = 0 and zero tokens, as registers
+                    h16x4 h0, l0;
+                    h16_split4(sc[0] * inv, h0, l0);
+                    ph[0] = h16_cat(h0, z4);
+                    pl[0] = h16_cat(l0, z4);
+                } else {
+#pragma unroll
+                    for (int s = 0; s < LS; ++s) h16_split8(sc[2 * s] * inv, sc[2 * s + 1] * inv, ph[s], pl[s]);
+                }
+#pragma unroll
+                for (int u = 0; u < NT; ++u) {
+                    f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
+#pragma unroll
+                    for (int s = 0; s < LS; ++s) {
+                        const char *blk = tr_base + 32 * s * RS + 32 * u;
+                        const h16x8 ah = h16_cat(lds_read_tr16(blk), LT == 1 ? z4 : lds_read_tr16(blk + 16 * RS));
+                        const h16x8 al = h16_cat(lds_read_tr16(blk + IMG), LT == 1 ? z4 : lds_read_tr16(blk + IMG + 16 * RS));
+                        MFMA_H(mm, ah, ph[s]);
+                        MFMA_H(cr, ah, pl[s]);
+                        MFMA_H(cr, al, ph[s]);
+                    }
+                    const f32x4 xt = f32x4{__builtin_fmaf(cr[0], H16_INV, mm[0]), __builtin_fmaf(cr[1], H16_INV, mm[1]),
+                                           __builtin_fmaf(cr[2], H16_INV, mm[2]), __builtin_fmaf(cr[3], H16_INV, mm[3])};
+                    if (q_ok) {  // xbar replaces qt in place (this lane's own bytes of the row)
+                        // image column 16 u + 4 g + i is k slot (2 (u % 2) + g / 2, 4 (g % 2) + i) of step u / 2 (see above)
+                        store_handoff(xrow + 32 * (u >> 1) + 16 * (g & 1) + 8 * (u & 1) + 4 * (g >> 1), xt);
+                    }
                 }
             }
-            // scores S[key][col] = sum_c T[key][c] Qt[col][c]
-            f32x4 sc[KT];
-#pragma unroll
-            for (int t = 0; t < KT; ++t) {
-                sc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-                if (!(used >> t & 1)) continue;
-                f32x4 mm = sc[t], cr = sc[t];
-#pragma unroll
-                for (int P = 0; P < NP; ++P) {
-                    const char *src = Ti + (16 * t + la) * RS + 64 * P + 16 * g;
-                    const h16x8 th = *reinterpret_cast<const h16x8 *>(src), tl = *reinterpret_cast<const h16x8 *>(src + IMG);
-                    MFMA_H(mm, th, qh[P]);
-                    MFMA_H(cr, th, ql[P]);
-                    MFMA_H(cr, tl, qh[P]);
-                }
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sc[t][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
-            }
-            // softmax over the unmasked keys in base 2 (QP: log2 e is folded into the Wk fragments): masked slots score -inf
-            float mx = -INFINITY;
-#pragma unroll
-            for (int t = 0; t < KT; ++t)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float sv = QP ? sc[t][i] : sc[t][i] * 1.4426950408889634f;
-                    sc[t][i] = (vmask >> (4 * t + i) & 1) ? sv : -INFINITY;
-                    mx = fmaxf(mx, sc[t][i]);
-                }
-            mx = fmaxf(mx, lane_xor16(mx));
-            mx = fmaxf(mx, lane_xor32(mx));
-            float sum = 0.f;
-#pragma unroll
-            for (int t = 0; t < KT; ++t)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float e = __builtin_amdgcn_exp2f(sc[t][i] - mx);  // slot 0 of a list is never masked: mx is finite
-                    sc[t][i] = e;
-                    sum += e;
-                }
-            sum += lane_xor16(sum);
-            sum += lane_xor32(sum);
-            const float inv = __builtin_amdgcn_rcpf(sum);
-            // Xbar^T[c][col] = sum_key T[key][c] P[key][col]
-            h16x8 ph[NS], pl[NS];
-#pragma unroll
-            for (int s = 0; s < NS; ++s) h16_split8(sc[2 * s] * inv, sc[2 * s + 1] * inv, ph[s], pl[s]);
-#pragma unroll
-            for (int u = 0; u < NT; ++u) {
-                f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
-#pragma unroll
-                for (int s = 0; s < NS; ++s) {
-                    const char *blk = tr_base + 32 * s * RS + 32 * u;
-                    const h16x8 ah = h16_cat(lds_read_tr16(blk), lds_read_tr16(blk + 16 * RS));
-                    const h16x8 al = h16_cat(lds_read_tr16(blk + IMG), lds_read_tr16(blk + IMG + 16 * RS));
-                    MFMA_H(mm, ah, ph[s]);
-                    MFMA_H(cr, ah, pl[s]);
-                    MFMA_H(cr, al, ph[s]);
-                }
-                const f32x4 xt = f32x4{__builtin_fmaf(cr[0], H16_INV, mm[0]), __builtin_fmaf(cr[1], H16_INV, mm[1]),
-                                       __builtin_fmaf(cr[2], H16_INV, mm[2]), __builtin_fmaf(cr[3], H16_INV, mm[3])};
-                if (q_ok) {  // xbar replaces qt in place (this lane's own bytes of the row)
-                    // image column 16 u + 4 g + i is k slot (2 (u % 2) + g / 2, 4 (g % 2) + i) of step u / 2 (see above)
-                    store_handoff(xrow + 32 * (u >> 1) + 16 * (g & 1) + 8 * (u & 1) + 4 * (g >> 1), xt);
-                }
-            }
-        }
+        };
+        if (front)
+            passes(std::integral_constant<bool, true>());
+        else
+            passes(std::integral_constant<bool, false>());
         wave_lds_sync();  // the next window rewrites the image
     }
+#undef KVH_WORD
 #undef KVH_LOAD_META
 #undef KVH_ISSUE_ROWS
 #undef KVH_ROW4
@@ -1309,7 +1383,10 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
     if constexpr (CG % 32 == 0) {
         if (kv16 && K > 16 && K <= 64) {  // split-fp16 operands in launch B (k_attn_kvh); A writes Qt pre-split
             constexpr int RS = KVH_RS(CG);
-            const int wgs = K <= 32 ? 4 : 2;  // resident workgroups per CU
+            // resident workgroups per CU.  (K <= 32 without blobs ran four at 128 registers and 6 spilled ones; with a pass body
+            // per tile set it spilled 45 there -- 159 / 76 us for the three launches on the flagship tables -- and takes 99 / 47 at
+            // three, against 106 / 48 before)
+            const int wgs = K <= 32 ? (CG >= 64 ? 3 : 4) : 2;  // (Cg = 32 fits 128 registers: four, as before)
             const dim3 kv_grid(cus * wgs / ng > 0 ? cus * wgs / ng : 1, ng);
             const size_t img = (size_t)ATTN_ROW_WAVES * 2 * 16 * RS;  // per key tile of 16 slots, all waves, hi + lo
             bool packed = HD == 16;
