@@ -1028,6 +1028,54 @@ int mssvt_pfn_sorted_64_128(const float *points, int point_stride, long long num
                             const float *bn2_var, float bn2_eps, int *workspace, float *x1_scratch, float *m1_scratch,
                             float *out, void *stream);
 
+/* DynamicVFE's TRAINING step over points grouped by voxel (csrc/vfe_train.hip): the index and reduction operators of
+ * ref pcdet/models/backbones_3d/vfe/dynamic_vfe.py:71-131 -- the kept points and unq_inv of :83-93, scatter_mean of :98,
+ * the features of :96-112, scatter_max + concat of PFNLayerV2 (:44-52) and the final scatter_max of :128-129 -- with
+ * torch_scatter's scatter_mean / scatter_max as oracle/gen_golden_vfe.py restates them (the gradient of a maximum split
+ * equally between the rows that attain it exactly).  No float atomics: every output element has one writer and every float
+ * sum a fixed order, so values and gradients are bit-identical run to run and across streams.  All kernels gfx950, wave64.
+ *
+ * mssvt_vfe_group (ref :83-93): point_voxel (P) int32 of mssvt_voxelize (-1: outside the grid) -> order (P) int32, the
+ *   original index of every kept point sorted by voxel and, inside a voxel, by ascending point index (entries behind P'
+ *   hold the dropped points); row_voxel (P) int32, the voxel of every grouped row (voxel_capacity behind P'); run_off
+ *   (voxel_capacity + 1) int32, rows [run_off[v], run_off[v + 1]) are voxel v's (a voxel no point carries: an empty run;
+ *   entries behind N repeat P'); sizes (2) int32 = [N, P'] left on the device for ONE host read.  num_voxels_dev: the device
+ *   word mssvt_voxelize left, or NULL: N = voxel_capacity.  An id outside [0, N) is dropped.  workspace: 16-byte aligned,
+ *   mssvt_vfe_group_workspace_bytes(P, voxel_capacity) bytes (0: size refused).
+ * mssvt_vfe_augment (ref :96-112, scatter_mean of :98), forward only: out (num_rows, C) f32, C = num_point_features +
+ *   3 with_cluster_center + 3 with_voxel_center + with_distance, row r from point order[r] of voxel row_voxel[r]:
+ *   [p[1 .. npf], xyz - mean_xyz(voxel), xyz - (cell * voxel_size + offset), |xyz|]; the mean from exact 64-bit fixed-point
+ *   sums (mssvt_voxel_mean_xyz's arithmetic).  voxel_coords (N, 4) int32 [b, z, y, x]; host_*3: HOST float[3], offset =
+ *   voxel_size / 2 + range_min; mean3_scratch (N, 3) f32, needed with the cluster centre.  A row whose point or voxel index
+ *   is out of range is written as zeros.
+ * mssvt_vfe_run_max_forward: x (num_rows, F) f32, run_off (num_voxels + 1) with run_off[0] = 0, ascending,
+ *   run_off[num_voxels] = num_rows.  concat != 0 (PFNLayerV2 :44-52): out (num_rows, 2F), row r = [x[r] ; max over r's run];
+ *   concat == 0 (ref :128-129): out (num_voxels, F) the maxima, an empty run a zero row.  The maximum of a run is taken from
+ *   its rows alone (never seeded with zero).  Two launches: the pieces of runs longer than MSSVT_VFE_TRAIN_CHUNK rows, then
+ *   the runs.  parts: mssvt_vfe_run_parts_floats(num_rows, F) floats, no need to clear.
+ * mssvt_vfe_run_max_backward: grad_x (num_rows, F).  concat != 0: saved = the forward's output (num_rows, 2F) (it holds x and
+ *   the broadcast maximum; maxima unused), grad_out (num_rows, 2F): gm = sum over the run's rows of grad_out[:, F:] in
+ *   ascending row order, grad_x[r] = grad_out[r, :F] + (x[r] == max ? gm / count : 0), count = rows of the run equal to the
+ *   maximum (-0 == +0).  concat == 0: saved = x, maxima (num_voxels, F) the forward's output, grad_out (num_voxels, F):
+ *   grad_x[r] = x[r] == max ? grad_out[v] / count : 0.  Non-finite inputs are not specified.
+ * F: a multiple of 4 in [4, 256]; float rows 16-byte aligned; rows and points below 2^31 - 256 (MSSVT_E_TOOLARGE beyond);
+ * bad sizes / null / unaligned pointers: MSSVT_E_BADARG before any launch.                                                */
+#define MSSVT_VFE_TRAIN_CHUNK 128
+long long mssvt_vfe_group_workspace_bytes(long long num_points, int voxel_capacity);
+int mssvt_vfe_group(const int *point_voxel, long long num_points, int voxel_capacity, const int *num_voxels_dev,
+                    int *order, int *row_voxel, int *run_off, int *sizes, void *workspace, long long workspace_bytes,
+                    void *stream);
+int mssvt_vfe_augment(const float *points, int point_stride, long long num_points, const int *order,
+                      const int *row_voxel, const int *run_off, int num_rows, int num_voxels, const int *voxel_coords,
+                      const float *host_voxel_size3, const float *host_offset3, int num_point_features,
+                      int with_cluster_center, int with_voxel_center, int with_distance, float *mean3_scratch, float *out,
+                      void *stream);
+long long mssvt_vfe_run_parts_floats(int num_rows, int F);
+int mssvt_vfe_run_max_forward(const float *x, const int *run_off, int num_rows, int num_voxels, int F, int concat,
+                              float *parts, float *out, void *stream);
+int mssvt_vfe_run_max_backward(const float *saved, const float *maxima, const float *grad_out, const int *run_off,
+                               int num_rows, int num_voxels, int F, int concat, float *parts, float *grad_x, void *stream);
+
 /* ======================================================================== *
  * Part 6 -- timing-only launches (csrc/ceiling.hip; no reference counterpart, nothing reads their output): the byte and
  *           instruction mix of k_ffn_ws / k_attn_kvh on the frame's real tables with every dependency between the

@@ -15,7 +15,7 @@ module by tests/golden/dynamic_vfe_train_*.npz: output, every parameter gradient
 import torch
 from torch import nn
 
-from . import _lib, voxelize
+from . import _lib, vfe_train, voxelize
 
 # the fused PFN of the default DynamicVFE configuration (csrc/pfn_fused.hip) over points grouped by voxel (csrc/pfn_sorted.hip:
 # no atomics on feature rows, no fills, x2 never stored); False: the atomic reductions of round 5 (kept: the comparator of
@@ -73,6 +73,9 @@ class DynamicVFE(nn.Module):
         for out_c in filters:
             self.pfn.append(nn.Sequential(nn.Linear(in_c, out_c), nn.BatchNorm1d(out_c), nn.ReLU(inplace=True)))
             in_c = out_c * 2
+        # opt-in: the training step's index and reduction operators on the HIP run kernels of csrc/vfe_train.hip
+        # (`_forward_train_fused`: deterministic, one host read); anything they do not cover takes `_forward_train`
+        self.fused_train = bool(get('FUSED_TRAIN', False))
 
     def get_output_feature_dim(self):
         return self.num_point_features
@@ -81,9 +84,44 @@ class DynamicVFE(nn.Module):
         if self.training:
             # BatchNorm1d on batch statistics must see exactly the rows the reference feeds it, and the reductions must
             # carry gradients: the differentiable branch (also under no_grad in train mode: the running statistics move)
+            if self.fused_train and self._fused_train_ok(batch_dict['points']):
+                return self._forward_train_fused(batch_dict)
             return self._forward_train(batch_dict)
         with torch.no_grad():
             return self._forward_eval(batch_dict)
+
+    def _fused_train_ok(self, points):
+        """What csrc/vfe_train.hip covers: float32 points on the GPU that carry no gradient, PFN widths that are multiples
+        of 4 up to 256, no autocast (the PFN layers would hand the run kernels half-precision rows)."""
+        return not torch.is_autocast_enabled() and points.is_cuda and points.dtype == torch.float32 and \
+            points.dim() == 2 and points.shape[0] > 0 and not points.requires_grad and points.shape[1] >= 1 + max(self.num_point_features_in, 3) and \
+            all(vfe_train.supported_width(blk[0].out_features) and blk[0].weight.dtype == torch.float32 for blk in self.pfn)
+
+    def _forward_train_fused(self, batch_dict):
+        """`_forward_train` on points grouped by voxel: the voxelizer's sorted voxel list (what torch.unique of the
+        reference key gives, ref :89-93), a stable grouping, the PFN input in one pass, and the reference's two reductions
+        as run kernels with a fixed summation order.  The PFN layers are the module's own (Linear, BatchNorm1d on batch
+        statistics, ReLU): BatchNorm sees the reference's rows in grouped order.  One host read: N and P' together."""
+        points = batch_dict['points'].contiguous()
+        coords, pv, n_dev = voxelize.voxelize_device(points, self.point_cloud_range_l, self.voxel_size_l, self.grid_size_l,
+                                                     batch_dict['batch_size'])
+        groups = vfe_train.group_points(pv, n_dev)
+        N, rows = groups.sizes.tolist()  # the step's one host read
+        if N == 0:
+            # no point inside the grid (rare): the torch branch starts over from the points, its own index work and host
+            # reads included -- what the grouping above cost is lost, nothing of it is reused
+            return self._forward_train(batch_dict)
+        voxel_coords, run_off = coords[:N], groups.run_off[:N + 1]
+        x = vfe_train.augment(points, groups, rows, N, voxel_coords, self.voxel_size_l,
+                              [self.voxel_size_l[k] / 2 + self.point_cloud_range_l[k] for k in range(3)],
+                              self.num_point_features_in, self.with_cluster_center, self.with_voxel_center, self.with_distance)
+        for i, blk in enumerate(self.pfn):
+            x = blk(x)
+            if i < len(self.pfn) - 1:
+                x = vfe_train.run_max_concat(x, run_off)
+        batch_dict['voxel_features'] = vfe_train.run_max(x, run_off)
+        batch_dict['voxel_coords'] = voxel_coords
+        return batch_dict
 
     def _forward_train(self, batch_dict):
         """ref dynamic_vfe.py:71-131 with torch_scatter's two reductions as differentiable torch operations."""
