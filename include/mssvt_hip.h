@@ -637,6 +637,13 @@ int mssvt_voxel_max(const float *features, int F, long long num_points, const in
 int mssvt_dense_bev(const float *features, int C, const int *map_table, int hash_size, const int *v_bs_cnt,
                     int batch_size, int x_max, int y_max, int z_max, float *out, void *stream);
 
+/* The same grid in channels-last memory (csrc/dense_bev.hip, k_dense_bev_nhwc), the hand-over to mssvt_bev_conv:
+ * out (B, Y, X, C*Z) f32 with channel c*Z + z -- the memory of dense().view(B, C*Z, Y, X) (ref height_compression.py:41-45)
+ * in torch.channels_last.  Every element written (a cell is a full row copy or zeros), bit-exact against mssvt_dense_bev.
+ * C % 4 == 0 (MSSVT_E_TOOLARGE otherwise); features and out 16-byte aligned.                                          */
+int mssvt_dense_bev_nhwc(const float *features, int C, const int *map_table, int hash_size, const int *v_bs_cnt,
+                         int batch_size, int x_max, int y_max, int z_max, float *out, void *stream);
+
 /* Deterministic segmented row sum -- replaces the atomicAdd accumulation of the reference's gather backward passes
  * (ref: group_features_grad_kernel_stack, pcdet/ops/mssvt/src/group_features_gpu.cu:15-47;
  * gather_points_grad_kernel_fast, pcdet/ops/pointnet2/pointnet2_batch/src/sampling_gpu.cu:53-90;
@@ -998,6 +1005,38 @@ int mssvt_frame_wait_words(void *frame, int *host_out, int num_words);
 int mssvt_linear_rows_h_supported(int K, int N);
 int mssvt_linear_rows_h(int M, int K, int N, const float *X, int ldx, const float *W, int transpose_w, const float *bias,
                         int relu, float out_scale, float *Y, int ldy, void *stream);
+
+/* y = act(scale[c] * conv(x, w) + shift[c]) on channels-last fp32 tensors with split-fp16 matrix operands
+ * (csrc/bev_conv.hip): the Conv2d + BatchNorm2d + ReLU triples of HeightCompression's compress_layers (ref
+ * pcdet/models/backbones_2d/map_to_bev/height_compression.py:20-39, applied to the grid of :41-45) and of BaseBEVBackbone's
+ * blocks / 1x1 deblocks (ref pcdet/models/backbones_2d/base_bev_backbone.py:30-78, forward :87-112) in eval mode.
+ * Inference only.  Tap sets: 3x3 with stride 1 or 2, dilation 1 or 2 and zero padding = dilation (ZeroPad2d(1) + padding 0
+ * at stride 2 is the padding-1 case); 1x1 with stride 1.  (cin, cout) in {(128,128), (128,256), (256,256), (32,32), (32,64),
+ * (64,64)}.  Output size Ho = (H + 2 p - d (k - 1) - 1) / stride + 1.
+ * mssvt_bev_conv_supported: 1 if the kernel covers the layer, else 0.
+ * mssvt_bev_conv_pack_bytes: size of a layer's packed blob (0: not covered); 64 header bytes (float [0] = 2^-e, [1] = 2^e, e the
+ *   exponent of max |w|), scale (cout) f32, shift (cout) f32, then per (128-wide slice of cout, tap, 128-wide chunk of cin) the
+ *   hi and the lo fp16 image of the weights divided by 2^e as v_mfma_f32_16x16x32_f16 operand fragments
+ *   [k step][column tile][lane][8] (tests/bev_conv_ref.py holds a host-side reader).
+ * mssvt_bev_conv_pack: weight (cout, cin, k, k) as Conv2d holds it, or (cin, cout, 1, 1) with transposed != 0 (ConvTranspose2d,
+ *   k = 1, stride 1); bias (cout) or NULL; BatchNorm2d in eval mode folded into scale / shift (bn_mean / bn_var (cout) or both
+ *   NULL: no batch norm; bn_weight / bn_bias (cout) or NULL: no affine); scale / shift stay fp32, they are not rounded into the
+ *   fp16 weights.  Two launches, no host read.  packed: 16-byte aligned, mssvt_bev_conv_pack_bytes bytes.
+ * mssvt_bev_conv: x (B, H, W, cin) f32, y (B, Ho, Wo, cout) f32, both 16-byte aligned; exp_workspace (B*H*W) int32, written
+ *   here (the largest |x| of every input pixel: each output pixel's operands are normalised by one exact power of two over
+ *   its receptive field, the weights by one for the tensor: no range precondition, and scaling x by a power of two scales
+ *   y bit for bit).  Never reads outside x, writes every element of y exactly once, bit-identical from call to call.
+ * Null / unaligned pointers and non-positive sizes: MSSVT_E_BADARG; a layer mssvt_bev_conv_supported refuses, or
+ * B*H*W >= 2^31 - 1024: MSSVT_E_TOOLARGE; neither launches anything.                                                  */
+#define MSSVT_BEV_CONV_WAVE_PIXELS 32   /* output pixels of one wavefront */
+#define MSSVT_BEV_CONV_BLOCK_PIXELS 256 /* output pixels of one workgroup */
+int mssvt_bev_conv_supported(int ksize, int cin, int cout, int stride, int dilation);
+long long mssvt_bev_conv_pack_bytes(int ksize, int cin, int cout);
+int mssvt_bev_conv_pack(const float *weight, int transposed, const float *bias, const float *bn_weight, const float *bn_bias,
+                        const float *bn_mean, const float *bn_var, float bn_eps, int ksize, int cin, int cout, void *packed,
+                        void *stream);
+int mssvt_bev_conv(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride,
+                   int dilation, int relu, int *exp_workspace, float *y, void *stream);
 
 /* DynamicVFE's two PFN layers in eval mode as two launches (csrc/pfn_fused.hip; ref
  * pcdet/models/backbones_3d/vfe/dynamic_vfe.py:96-131, PFNLayerV2 :14-52), default configuration: 5 point features + cluster

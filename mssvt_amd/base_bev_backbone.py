@@ -4,7 +4,12 @@ Drop-in for pcdet/models/backbones_2d/base_bev_backbone.py:6-114: constructor ``
 config keys LAYER_NUMS / LAYER_STRIDES / NUM_FILTERS / UPSAMPLE_STRIDES / NUM_UPSAMPLE_FILTERS, ``num_bev_features``,
 ``forward(data_dict)`` reading ``spatial_features`` and writing ``spatial_features_2d`` (+ ``spatial_features_{s}x``),
 and the state-dict keys ``blocks.{i}.{k}.*`` / ``deblocks.{i}.{k}.*`` (a reference checkpoint loads by key).  Dense
-convolutions run through the library (MIOpen) -- they are not on the sparse hot path."""
+convolutions run through the library (MIOpen) -- they are not on the sparse hot path.
+
+``fused_convs`` (off by default; yaml key ``FUSED_CONVS``): in eval mode with autograd off, an fp32 GPU input and ``AMP`` off,
+the tensors are channels-last and every Conv + BN + ReLU triple that ``bev_conv.routed`` accepts (the 1x1 stride-1 deblock
+included) runs on the split-fp16 kernel of csrc/bev_conv.hip; the 2x2 stride-2 transposed deblock and any other layer run
+through the library on the same tensors.  Shapes and ``data_dict`` keys are unchanged, only strides differ."""
 import torch
 from torch import nn
 
@@ -47,9 +52,30 @@ class BaseBEVBackbone(nn.Module):
                 nn.ConvTranspose2d(c_out, c_out, up_strides[-1], stride=up_strides[-1], bias=False), bn(c_out), nn.ReLU()))
         self.num_bev_features = c_out
         self.use_amp = bool(_get(model_cfg, "AMP", False))
+        self.fused_convs = bool(_get(model_cfg, "FUSED_CONVS", False))
+
+    def _forward_fused(self, data_dict, feats):
+        from . import bev_conv
+        x, ups = feats.contiguous(memory_format=torch.channels_last), []
+        for i, blk in enumerate(self.blocks):
+            x = bev_conv.run_layers(blk, x)
+            data_dict["spatial_features_%dx" % int(feats.shape[2] / x.shape[2])] = x
+            ups.append(bev_conv.run_layers(self.deblocks[i], x) if len(self.deblocks) > 0 else x)
+        if len(ups) > 1:
+            x = torch.cat(ups, dim=1)
+        elif len(ups) == 1:
+            x = ups[0]
+        if len(self.deblocks) > len(self.blocks):
+            x = bev_conv.run_layers(self.deblocks[-1], x)
+        data_dict["spatial_features_2d"] = x
+        return data_dict
 
     def forward(self, data_dict):
         feats = data_dict["spatial_features"]
+        if self.fused_convs:
+            from . import bev_conv
+            if bev_conv.switch_applies(self, feats):
+                return self._forward_fused(data_dict, feats)
         with torch.autocast(device_type=feats.device.type, enabled=self.use_amp and feats.is_cuda):
             x, ups = feats, []
             for i, blk in enumerate(self.blocks):

@@ -1,0 +1,190 @@
+"""Dense BEV convolutions on split-fp16 matrix instructions (csrc/bev_conv.hip): ``y = act(scale * conv(x, w) + shift)``
+on channels-last fp32 tensors, inference only.
+
+Stands for the Conv2d + BatchNorm2d + ReLU triples of the reference's ``HeightCompression.compress_layers``
+(pcdet/models/backbones_2d/map_to_bev/height_compression.py:20-39) and ``BaseBEVBackbone`` blocks / 1x1 deblocks
+(pcdet/models/backbones_2d/base_bev_backbone.py:30-78) in eval mode.  A layer is turned into one packed blob on the
+device (fp16 hi / lo weight images + the folded BatchNorm as fp32 scale / shift) by ``pack``; ``conv_bn_act`` runs it.
+There is no CPU path.
+
+``ROUTED`` lists the product layer shapes the modules send here when their ``fused_convs`` switch is on: exactly those
+whose slowest run beat the library's fastest in tools/time_bev_conv.py (profiles/bev_conv_times.json, DESIGN section
+5.5's rule).  Every covered shape stays reachable through ``conv_bn_act``.
+"""
+import weakref
+
+import torch
+from torch import nn
+
+from . import _lib
+from ._lib import MssvtHipError
+
+# the kernel's tiles (include/mssvt_hip.h: MSSVT_BEV_CONV_WAVE_PIXELS / MSSVT_BEV_CONV_BLOCK_PIXELS)
+WAVE_PIXELS = 32
+BLOCK_PIXELS = 256
+
+CHANNEL_SHAPES = ((128, 128), (128, 256), (256, 256), (32, 32), (32, 64), (64, 64))
+# (ksize, cin, cout, stride, dilation) of the product layers (mssvt.yaml) that cleared the routing rule on an MI355X
+# (profiles/bev_conv_times.json: all five covered shapes of the configuration cleared it, at B = 1 and B = 4)
+ROUTED = frozenset({
+    (3, 128, 128, 1, 1), (3, 128, 128, 1, 2), (3, 128, 256, 2, 1), (3, 256, 256, 1, 1), (1, 128, 256, 1, 1),
+})
+# the narrow shapes exist so that the reference-run goldens (32 / 64 channels) pass through the kernel: no product
+# configuration has them, they are not timed, and the modules route them whenever the switch is on
+GOLDEN_CHANNELS = frozenset({(32, 32), (32, 64), (64, 64)})
+
+
+def _pair(v):
+    return (int(v[0]), int(v[1])) if isinstance(v, (tuple, list)) else (int(v), int(v))
+
+
+def layer_shape(conv, pad=None):
+    """(ksize, cin, cout, stride, dilation, transposed) of a layer the kernel's tap sets can express, else None.  `pad`
+    overrides the convolution's own padding (a ZeroPad2d(1) in front of a padding-0 convolution: pad = 1)."""
+    transposed = isinstance(conv, nn.ConvTranspose2d)
+    if not isinstance(conv, (nn.Conv2d, nn.ConvTranspose2d)) or conv.groups != 1:
+        return None
+    if not transposed and conv.padding_mode != "zeros":
+        return None
+    k, s, d = _pair(conv.kernel_size), _pair(conv.stride), _pair(conv.dilation)
+    if isinstance(conv.padding, str) or k[0] != k[1] or s[0] != s[1] or d[0] != d[1]:
+        return None
+    p = _pair(conv.padding) if pad is None else _pair(pad)
+    if p[0] != p[1]:
+        return None
+    if transposed and (k[0] != 1 or s[0] != 1 or _pair(conv.output_padding) != (0, 0)):
+        return None
+    if p[0] != (d[0] if k[0] == 3 else 0):
+        return None
+    return (k[0], int(conv.in_channels), int(conv.out_channels), s[0], d[0], transposed)
+
+
+def supported(conv, bn=None, pad=None):
+    """True if `conv` (+ an eval-mode BatchNorm2d `bn`) is a layer ``pack`` / ``conv_bn_act`` cover."""
+    shape = layer_shape(conv, pad)
+    if shape is None or conv.weight.dtype != torch.float32 or not conv.weight.is_cuda:
+        return False
+    if bn is not None and not (isinstance(bn, nn.BatchNorm2d) and bn.running_mean is not None and bn.running_var is not None
+                               and bn.num_features == shape[2]):
+        return False
+    return bool(_lib.lib().mssvt_bev_conv_supported(*shape[:5]))
+
+
+def routed(conv, bn=None, pad=None):
+    """True if the modules send this layer to the kernel when their switch is on."""
+    if not supported(conv, bn, pad):
+        return False
+    shape = layer_shape(conv, pad)
+    return shape[:5] in ROUTED or shape[1:3] in GOLDEN_CHANNELS
+
+
+class Packed(object):
+    """One layer as the kernel reads it: `blob` (uint8, device) and the layer's geometry."""
+    __slots__ = ("blob", "ksize", "cin", "cout", "stride", "dilation", "transposed")
+
+    def __init__(self, blob, shape):
+        self.blob = blob
+        self.ksize, self.cin, self.cout, self.stride, self.dilation, self.transposed = shape
+
+    def out_size(self, h, w):
+        return (h - 1) // self.stride + 1, (w - 1) // self.stride + 1
+
+
+_cache = weakref.WeakKeyDictionary()  # conv module -> (key, Packed)
+
+
+def _tensors(conv, bn):
+    ts = [conv.weight, conv.bias]
+    if bn is not None:
+        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
+    return ts
+
+
+def _key(conv, bn, pad):
+    # tensor identity, storage and version: load_state_dict and an optimizer step write in place (version), .to() and a
+    # re-assigned parameter change the identity or the storage
+    k = [id(bn), None if bn is None else float(bn.eps), pad]
+    for t in _tensors(conv, bn):
+        k.append(None if t is None else (id(t), t.data_ptr(), t._version, str(t.device)))
+    return tuple(k)
+
+
+@torch.no_grad()
+def pack(conv, bn=None, pad=None):
+    """The packed blob of a layer (cached per `conv` module; rebuilt when a parameter or running statistic changed).
+    Runs on the device on the current stream, no host read."""
+    key = _key(conv, bn, pad)
+    hit = _cache.get(conv)
+    if hit is not None and hit[0] == key:
+        return hit[1]
+    if not supported(conv, bn, pad):
+        raise MssvtHipError("bev_conv.pack: layer not covered (%r, %r)" % (conv, bn))
+    shape = layer_shape(conv, pad)
+    ksize, cin, cout = shape[:3]
+    ts = _tensors(conv, bn) + ([None] * 4 if bn is None else [])
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.device == conv.weight.device):
+            raise MssvtHipError("bev_conv.pack: parameters must be fp32 tensors on one GPU")
+    w, bias, bn_w, bn_b, bn_m, bn_v = [None if t is None else t.detach().contiguous() for t in ts]
+    nbytes = _lib.lib().mssvt_bev_conv_pack_bytes(ksize, cin, cout)
+    blob = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("mssvt_bev_conv_pack", _lib.ptr(w), int(shape[5]), _lib.ptr(bias), _lib.ptr(bn_w), _lib.ptr(bn_b),
+                  _lib.ptr(bn_m), _lib.ptr(bn_v), 0.0 if bn is None else float(bn.eps), ksize, cin, cout, _lib.ptr(blob),
+                  _lib.stream())
+    packed = Packed(blob, shape)
+    _cache[conv] = (key, packed)
+    return packed
+
+
+def is_channels_last(x):
+    """4-D and NHWC in memory (the logical shape stays (B, C, H, W))."""
+    return x.dim() == 4 and x.permute(0, 2, 3, 1).is_contiguous()
+
+
+def conv_bn_act(x, packed, relu=True):
+    """`x` (B, cin, H, W) fp32 on the GPU, channels-last in memory -> (B, cout, Ho, Wo) of the same kind."""
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and is_channels_last(x)):
+        raise MssvtHipError("bev_conv.conv_bn_act needs a 4-D fp32 GPU tensor that is channels-last in memory (no CPU path)")
+    if x.requires_grad and torch.is_grad_enabled():
+        raise MssvtHipError("bev_conv.conv_bn_act is inference only (autograd is on for this input)")
+    B, C, H, W = x.shape
+    if C != packed.cin or packed.blob.device != x.device:
+        raise MssvtHipError("bev_conv.conv_bn_act: input has %d channels on %s, the layer takes %d on %s"
+                            % (C, x.device, packed.cin, packed.blob.device))
+    if min(B, H, W) < 1 or x.data_ptr() % 16:
+        raise MssvtHipError("bev_conv.conv_bn_act: empty or unaligned input")
+    ho, wo = packed.out_size(H, W)
+    y = torch.empty((B, ho, wo, packed.cout), dtype=torch.float32, device=x.device)
+    emap = torch.empty(B * H * W, dtype=torch.int32, device=x.device)
+    _lib.call("mssvt_bev_conv", x.data_ptr(), B, H, W, C, packed.blob.data_ptr(), packed.ksize, packed.cout, packed.stride,
+              packed.dilation, int(bool(relu)), emap.data_ptr(), y.data_ptr(), _lib.stream())
+    return y.permute(0, 3, 1, 2)
+
+
+def switch_applies(module, x):
+    """The conditions under which a module's `fused_convs` takes effect: on, eval mode, autograd off, fp32 on the GPU, no AMP."""
+    return bool(getattr(module, "fused_convs", False)) and not module.training and not torch.is_grad_enabled() \
+        and not getattr(module, "use_amp", False) and x.is_cuda and x.dtype == torch.float32
+
+
+def run_layers(layers, x):
+    """A Conv / BatchNorm / ReLU stack (`layers`: the modules in order) on a channels-last tensor: every routed
+    Conv + BN (+ ReLU) triple through the kernel, every other module through the library on the same tensors."""
+    layers = list(layers)
+    i, n = 0, len(layers)
+    while i < n:
+        m, pad, ci = layers[i], None, i
+        if isinstance(m, nn.ZeroPad2d) and tuple(m.padding) == (1, 1, 1, 1) and i + 1 < n \
+                and isinstance(layers[i + 1], nn.Conv2d) and _pair(layers[i + 1].padding) == (0, 0):
+            pad, ci = 1, i + 1
+        conv = layers[ci]
+        bn = layers[ci + 1] if ci + 1 < n and isinstance(layers[ci + 1], nn.BatchNorm2d) else None
+        if isinstance(conv, (nn.Conv2d, nn.ConvTranspose2d)) and bn is not None and routed(conv, bn, pad):
+            relu = ci + 2 < n and isinstance(layers[ci + 2], nn.ReLU)
+            x = conv_bn_act(x, pack(conv, bn, pad), relu)
+            i = ci + (3 if relu else 2)
+        else:
+            x = m(x)
+            i += 1
+    return x

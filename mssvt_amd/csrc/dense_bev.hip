@@ -182,3 +182,52 @@ extern "C" int mssvt_dense_bev(const float *features, int C, const int *map_tabl
         features, reinterpret_cast<const slot_t *>(map_table), v_bs_cnt, batch_size, x_max, y_max, z_max, C, hash_size, out);
     return mssvt_launch_status();
 }
+
+// The same gather in channels-last memory for the BEV convolutions of csrc/bev_conv.hip: out (B, Y, X, C * Z) with channel
+// c * Z + z -- the memory of dense().view(B, C * Z, Y, X) in torch.channels_last (ref height_compression.py:41-45).  One
+// lane owns four consecutive channels of a cell: with Z == 1 they are 16 bytes of the cell's row (a cell is a full row copy or
+// zeros); otherwise each of them is looked up on its own (z = channel % Z).  The lanes of a cell repeat its probes (cache
+// hits; a wave covers 256 channels).  Pure copy: bit-exact against mssvt_dense_bev.
+__global__ void __launch_bounds__(256)
+    k_dense_bev_nhwc(const float *features, const slot_t *table, const int *v_bs_cnt, int B, int X, int Y, int Z, int C,
+                     int hash_size, float *out) {
+    const int CZ = C * Z, quads = CZ / 4;
+    const long long total = (long long)B * Y * X * quads;
+    for (long long id = (long long)blockIdx.x * blockDim.x + threadIdx.x; id < total; id += (long long)gridDim.x * blockDim.x) {
+        const int q = (int)(id % quads);
+        const long long cell = id / quads;
+        const int x = (int)(cell % X), y = (int)((cell / X) % Y), b = (int)(cell / ((long long)X * Y));
+        int vstart = 0;
+        for (int k = 0; k < b; ++k) vstart += v_bs_cnt[k];
+        const slot_t *tab = table + (size_t)b * hash_size;
+        float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (Z == 1) {
+            const int sv = table_find(x * Y + y, hash_size, tab);  // x-major key, z = 0
+            if (sv != MSSVT_EMPTY) o = *reinterpret_cast<const float4 *>(features + (size_t)(vstart + sv) * C + 4 * q);
+        } else {
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int ch = 4 * q + i, c = ch / Z, z = ch - c * Z;
+                const int sv = table_find(x * Y * Z + y * Z + z, hash_size, tab);
+                if (sv != MSSVT_EMPTY) v[i] = features[(size_t)(vstart + sv) * C + c];
+            }
+            o = make_float4(v[0], v[1], v[2], v[3]);
+        }
+        *reinterpret_cast<float4 *>(out + (size_t)id * 4) = o;
+    }
+}
+
+extern "C" int mssvt_dense_bev_nhwc(const float *features, int C, const int *map_table, int hash_size, const int *v_bs_cnt,
+                                    int batch_size, int x_max, int y_max, int z_max, float *out, void *stream) {
+    if (!features || !map_table || !v_bs_cnt || !out || C <= 0 || hash_size <= 0 || batch_size <= 0 || x_max <= 0 ||
+        y_max <= 0 || z_max <= 0 || ((reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(features)) & 15))
+        return MSSVT_E_BADARG;
+    if (C % 4 != 0) return MSSVT_E_TOOLARGE;  // 16-byte pieces of a row
+    const long long total = (long long)batch_size * y_max * x_max * (C * z_max / 4);
+    long long grid = (total + 255) / 256;
+    if (grid > 65536 * 4) grid = 65536 * 4;
+    k_dense_bev_nhwc<<<(int)grid, 256, 0, (hipStream_t)stream>>>(features, reinterpret_cast<const slot_t *>(map_table), v_bs_cnt,
+                                                                 batch_size, x_max, y_max, z_max, C, hash_size, out);
+    return mssvt_launch_status();
+}

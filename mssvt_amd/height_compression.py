@@ -9,6 +9,11 @@ What differs is where the dense grid comes from: ``SparseTensor.dense()`` of thi
 kernel (``k_dense_bev``, csrc/dense_bev.hip) that writes ``(B, C, Z, Y, X)`` directly -- no zero fill, no
 scatter, no permute copy -- and ``(B, C*Z, Y, X)`` is a view of it.  The optional 3x3 compression convs are
 plain library convolutions (MIOpen through torch): they are dense, regular work outside the sparse path.
+
+``fused_convs`` (off by default; yaml key ``FUSED_CONVS``): in eval mode with autograd off, fp32 features on the GPU and
+``AMP`` off, the grid is gathered channels-last (``mssvt_dense_bev_nhwc``) and every Conv + BN + ReLU triple that
+``bev_conv.routed`` accepts runs on the split-fp16 kernel of csrc/bev_conv.hip; the other layers run through the library
+on the same channels-last tensors.  The output keeps its logical ``(B, C, H, W)`` shape, only its strides differ.
 """
 import torch
 import torch.nn as nn
@@ -30,6 +35,7 @@ class HeightCompression(nn.Module):
         dilations = _cfg_get(model_cfg, "LAYER_DIALATIONS", [1, 1, 2])  # (sic) the reference's key
         paddings = _cfg_get(model_cfg, "LAYER_PADDINGS", [1, 1, 2])
         self.use_amp = bool(_cfg_get(model_cfg, "AMP", False))
+        self.fused_convs = bool(_cfg_get(model_cfg, "FUSED_CONVS", False))
         self.compress_layers = None
         if n_layers:
             c = self.num_bev_features
@@ -41,6 +47,15 @@ class HeightCompression(nn.Module):
 
     def forward(self, batch_dict):
         sp = batch_dict["encoded_spconv_tensor"]
+        if self.fused_convs:
+            from . import bev_conv
+            if bev_conv.switch_applies(self, sp.features):
+                bev = sp.dense_nhwc()  # (B, C * Z, Y, X), channels-last in memory
+                if self.compress_layers is not None:
+                    bev = bev_conv.run_layers(self.compress_layers, bev)
+                batch_dict["spatial_features"] = bev
+                batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
+                return batch_dict
         with torch.autocast("cuda", enabled=self.use_amp and sp.features.is_cuda):
             dense = sp.dense()  # (B, C, Z, Y, X), gathered in one pass
             b, c, d, h, w = dense.shape

@@ -111,6 +111,16 @@ def main(out_path):
             out["vfe_atomic"] = vfe(dict(points=pt, batch_size=B))["voxel_features"].cpu().numpy()  # pfn_fused.hip
         finally:
             dynamic_vfe.SORTED_PFN = True
+    # --- csrc/bev_conv.hip: the 128-wide and the 256-wide form (two output slices, two input chunks) and a narrow one
+    from mssvt_amd import bev_conv
+    g = torch.Generator().manual_seed(12)
+    for k, cin, cout, stride, dil in ((3, 128, 128, 1, 2), (3, 256, 256, 1, 1), (3, 128, 256, 2, 1), (3, 32, 64, 1, 1)):
+        conv = torch.nn.Conv2d(cin, cout, k, stride=stride, padding=dil, dilation=dil, bias=False)
+        with torch.no_grad():
+            conv.weight.copy_(torch.randn(conv.weight.shape, generator=g))
+            xr = torch.randn(2, 23, 29, cin, generator=g).clamp_(min=0).to(DEV).permute(0, 3, 1, 2)
+            out["bev_conv_%d_%d_s%d_d%d" % (cin, cout, stride, dil)] = \
+                bev_conv.conv_bn_act(xr, bev_conv.pack(conv.to(DEV), None), True).cpu().numpy()
     np.savez(out_path, **out)
     print("schedule probe: %d arrays from %s -> %s" % (len(out) - 1, _lib.LIB_PATH, out_path))
 
