@@ -292,6 +292,23 @@ int mssvt_window_plan_two_vox(
     const int *host_footprint4, const int *packed_offsets, const int *column_vbase, const int *level_status_dev,
     const int *win_counts_dev, int *vox_win, void *stream);
 
+/* mssvt_window_plan_two_vox that also writes, per window and key scale, whether the key list holds a row in a slot
+ * 16 .. key_num_sample-1: live1 / live2 (win_capacity) int32, 1 = such a slot is live, 0 = every live key sits in slots
+ * 0 .. 15; written for every window below *num_wins_dev.  Every other output has the bits it has without them. */
+int mssvt_window_plan_two_live(
+    int x_max, int y_max, int z_max, int x_ws, int y_ws, int z_ws, int max_num_odd, int max_num_even,
+    int max_num_win1, int max_num_win2, int hash_size, int batch_size, int num_odd, int num_even,
+    int num_win1, int num_win2, const int *vox_query_odd, const int *vox_query_even,
+    const int *vox_query_win1, const int *vox_query_win2, int key_num_sample, const int *win_indices,
+    const int *num_wins_dev, int win_capacity, const int *xyz_to_vidx, const int *v_bs_cnt,
+    int *ind_odd, int *ind_even, int *ind_win1, int *k_ind1, int *k_ind2, unsigned char *k_mask1,
+    unsigned char *k_mask2, int *win_vstart, int *owner_win1, int *owner_odd, int *owner_even,
+    const int *indices, const float *host_voxel_size3, const float *host_range_min3,
+    const float *host_win_size3, float *qmeta_odd, float *qmeta_even, float *qmeta_win1, float *kmeta1,
+    float *kmeta2, float *wcentre, int *nq_valid, const unsigned long long *occ_columns,
+    const int *host_footprint4, const int *packed_offsets, const int *column_vbase, const int *level_status_dev,
+    const int *win_counts_dev, int *vox_win, int *live1, int *live2, void *stream);
+
 /* The interpolation tables of mssvt_window_plan_two(num_tabs > 0), byte for byte, from a finished plan: one lane per
  * (voxel, table).  vox_win from mssvt_window_plan_two_vox; nq_valid (3, win_capacity) and the qmeta of every list a table
  * names from the same plan (.w of a slot = the global feature row of its voxel); indices (N,4); the host_tab_* arrays as
@@ -346,6 +363,22 @@ int mssvt_plan_order_multi(int num_sets, const int *num_wins_dev, const int *con
                            int *const *host_q_off, float *const *host_qrow_meta, int *const *host_qrow_src,
                            int *const *host_num_rows, void *stream);
 
+/* mssvt_plan_order_multi that also builds, in the same launches, the step lists of mssvt_block_attention_kv16_steps: one
+ * per (query list i, head group g), host_steps[i * num_groups + g] (2 x win_capacity) int32 and host_num_steps[..] (1),
+ * from the list's nq_valid and host_live[g] (win_capacity; mssvt_window_plan_two_live: 1 = the window needs the upper
+ * key tile in group g).  A step is (wA, wB), wB = -1 for one window alone.  Every window of perm is in exactly one step;
+ * a pair holds two distinct windows with live == 0 and equal min(nq_valid, 256); steps come in descending order of that
+ * count; of the live == 0 windows of one count at most one is alone (who pairs with whom is free).  Nothing is written at
+ * or behind step *num_steps.  scratch: mssvt_plan_order_steps_scratch_ints(num_sets, num_groups) ints.
+ * num_sets * (1 + num_groups) <= 12 (MSSVT_E_TOOLARGE).  perm, q_off, the rows and the counts as mssvt_plan_order_multi. */
+long long mssvt_plan_order_steps_scratch_ints(int num_sets, int num_groups);
+int mssvt_plan_order_steps(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid,
+                           const int *host_nq, const float *const *host_qmeta, int win_capacity,
+                           int row_capacity, int *const *host_perm, int *const *host_num_active,
+                           int *const *host_q_off, float *const *host_qrow_meta, int *const *host_qrow_src,
+                           int *const *host_num_rows, int num_groups, const int *const *host_live,
+                           int *const *host_steps, int *const *host_num_steps, int *scratch, void *stream);
+
 /* Fused attention of a Block, all head groups (group g = channels [c0[g], c0[g]+Cg[g]),
  * Cg = heads[g]*head_dim <= 64, attends to key scale g): gathers + positional MLP +
  * MixedScaleAttention (ref mssvt_backbone.py:260-295, mssvt_utils.py:112-150) for every valid
@@ -383,6 +416,20 @@ int mssvt_block_attention_kv16(
     const float *const *host_Wkv, const float *const *host_bkv, const float *const *host_Wo,
     const float *const *host_bo, const float *Wpos, const float *bpos, float *qbuf, float *attn,
     const void *const *host_packed, void *stream);
+
+/* mssvt_block_attention_kv16 whose window launch walks the step lists of mssvt_plan_order_steps (host_steps[g] /
+ * host_num_steps[g]: head group g's list of this block's query pattern): the two windows of a step share a wavefront, window
+ * B's key slots 0 .. 15 in the upper key tile, each column masking the other window's tile.  The attention rows have the
+ * bits of mssvt_block_attention_kv16 on the same inputs.  Only the Q' hand-off form takes pairs (host_packed blobs for
+ * every group, head_dim 16, 16 < key_num_sample <= 32, equal group widths): MSSVT_E_TOOLARGE otherwise, nothing launched. */
+int mssvt_block_attention_kv16_steps(
+    int C, int num_groups, const int *host_c0, const int *host_cg, const int *host_heads, int head_dim, float scale,
+    int nq, int key_num_sample, const float *xhat, const int *num_active_dev, const int *perm, const int *q_off,
+    const int *nq_valid, const int *num_rows_dev, int row_capacity, const float *qrow_meta, const int *qrow_src,
+    const float *const *host_kmeta, const float *wcentre, const float *const *host_Wq, const float *const *host_bq,
+    const float *const *host_Wkv, const float *const *host_bkv, const float *const *host_Wo,
+    const float *const *host_bo, const float *Wpos, const float *bpos, float *qbuf, float *attn,
+    const void *const *host_packed, const int *const *host_steps, const int *const *host_num_steps, void *stream);
 
 /* Split-fp16 fragments of one head group's projections for mssvt_block_attention_kv16, in MFMA operand order: Wq
  * (Cg,Cg), Wkv (2Cg,Cg: K rows then V rows; the softmax scale folded into the K fragments, scale x log2 e into their

@@ -73,6 +73,11 @@ struct AttnArgs {
     float *attn;
     int row_capacity;  // rows of qbuf / the compact row arrays
     const void *packed;  // split-fp16 weight fragments of this group (mssvt_attn_pack_weights) or null
+    // work list of k_attn_kvh: *num_steps steps of step_stride ints.  Stride 1: `perm`, every step one window.  Stride 2:
+    // (wA, wB) from mssvt_plan_order_steps, wB = -1 for a single; a pair = two windows of this group whose live keys all
+    // sit in slots 0 .. 15 (k_attn_kvh<.., 2, true> only)
+    const int *steps, *num_steps;
+    int step_stride;
 };
 
 // head groups of equal shape run in ONE launch: blockIdx.y = group (their work is independent: channel
@@ -1072,7 +1077,12 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
     // entries leave as soon as the count is there and travel during the LDS stores and the barrier.  (Reading the order
     // ahead of the count would save one more trip, but the entry points carry no window capacity, so no index of `perm`
     // at or beyond *num_wins can be bounded by its allocation.)
-    const int n_act_v = KVH_WORD(a.num_wins, 0);
+    // PAIRS: a step may hold two one-tile windows -- window B's slots 0 .. 15 take key tile 1, the query lists are concatenated
+    // and a column masks the other window's tile: exp2(-inf) = +0 in the softmax sum, token x (+0) in the second product, so
+    // every window's rows have the bits of its run as a single
+    constexpr bool PAIRS = KT == 2 && QP;
+    const int sstr = a.step_stride;
+    const int n_act_v = KVH_WORD(a.num_steps, 0);
     // positional MLP operand of this lane: A row la of tile u <-> channel (16 * u + la), input g: the weight of the
     // relative offset (g < 3) | bias + window-centre part (g = 3: summed over the three lanes that hold its weights)
     float wrel[NT], wctr[NT];
@@ -1096,10 +1106,14 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
     const int w_last = n_act - 1;
     // the wave's first three windows, loaded without a branch: indices <= w_last, inside the *num_wins entries that
     // mssvt_plan_order wrote; with no active window at all the three loads read the count word again instead
-    const int *perm0 = n_act > 0 ? a.perm : a.num_wins;
-    const int w_p0 = KVH_WORD(perm0, max(min(wi, w_last), 0));
-    const int w_p1 = KVH_WORD(perm0, max(min(wi + wstep, w_last), 0));
-    const int w_p2 = KVH_WORD(perm0, max(min(wi + 2 * wstep, w_last), 0));
+    const int *perm0 = n_act > 0 ? a.steps : a.num_steps;
+    const int sst0 = n_act > 0 ? sstr : 0, sb0 = PAIRS && n_act > 0 ? sstr - 1 : 0;  // (window B: the step's last word)
+    const int w_p0 = KVH_WORD(perm0, max(min(wi, w_last), 0) * sst0);
+    const int w_p1 = KVH_WORD(perm0, max(min(wi + wstep, w_last), 0) * sst0);
+    const int w_p2 = KVH_WORD(perm0, max(min(wi + 2 * wstep, w_last), 0) * sst0);
+    const int w_pb0 = KVH_WORD(perm0, max(min(wi, w_last), 0) * sst0 + sb0);
+    const int w_pb1 = KVH_WORD(perm0, max(min(wi + wstep, w_last), 0) * sst0 + sb0);
+    const int w_pb2 = KVH_WORD(perm0, max(min(wi + 2 * wstep, w_last), 0) * sst0 + sb0);
     if (QP) {  // before any wave can leave: every wave of the workgroup meets at the barrier
         attn_stage16_store<WK16, ATTN_ROW_WAVES * MSSVT_WAVE>(lds4, wk_v);
         __syncthreads();
@@ -1116,21 +1130,37 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
     // load issued before it, the next window's rows among them -- lands right behind the load: one full round trip per
     // window, the pipeline undone.  Their byte offsets therefore carry a zero the compiler cannot see through (`vz`): the
     // words stay in vector registers until readfirstlane at the point of use, one iteration later.
-    int w_p;
-    float4 wc_m, km_m[KT];
-    int nqv_m, qbase_m;
+    int w_p, w_pb;
+    float4 wc_m, wcb_m, km_m[KT];
+    int nqv_m, qbase_m, nqvb_m, qbaseb_m;
+    bool pair_m = false;  // (wave-uniform) the step whose metadata is in flight holds two windows
 #define KVH_LOAD_META()                                                                    \
     {                                                                                      \
         const int w_ = __builtin_amdgcn_readfirstlane(w_p);                                \
+        int wb_ = w_;                                                                      \
+        if (PAIRS) {                                                                       \
+            const int b_ = __builtin_amdgcn_readfirstlane(w_pb);                           \
+            pair_m = sstr == 2 && b_ >= 0;                                                 \
+            wb_ = pair_m ? b_ : w_;                                                        \
+        }                                                                                  \
         wc_m = a.wcentre[w_];                                                              \
         nqv_m = KVH_WORD(a.nq_valid, w_);                                                  \
         qbase_m = KVH_WORD(a.q_off, w_);                                                   \
-        _Pragma("unroll") for (int t = 0; t < KT; ++t)                                     \
+        if (PAIRS) {                                                                       \
+            wcb_m = a.wcentre[wb_];                                                        \
+            nqvb_m = KVH_WORD(a.nq_valid, wb_);                                            \
+            qbaseb_m = KVH_WORD(a.q_off, wb_);                                             \
+        }                                                                                  \
+        _Pragma("unroll") for (int t = 0; t < KT; ++t) {                                   \
+            const int wt_ = PAIRS && t == 1 ? wb_ : w_;                                    \
+            const int sl_ = PAIRS && t == 1 && pair_m ? la : 16 * t + la;                  \
             km_m[t] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(    \
-                km_rs, ((unsigned)w_ * (unsigned)K + (unsigned)min(16 * t + la, K - 1)) * 16u, 0, 0)); \
+                km_rs, ((unsigned)wt_ * (unsigned)K + (unsigned)min(sl_, K - 1)) * 16u, 0, 0)); \
+        }                                                                                  \
     }
-    float4 wc_r;
-    int nqv_r, qbase_r;
+    float4 wc_r, wcb_r;
+    int nqv_r, qbase_r, nqvb_r = 0, qbaseb_r = 0;
+    bool pair_r = false;
     float rel_r[KT];
     unsigned vmask_r, used_r;
     f32x4 T1n[KT][NT];
@@ -1145,14 +1175,23 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
         wc_r = wc_m;                                                                       \
         nqv_r = __builtin_amdgcn_readfirstlane(nqv_m);                                     \
         qbase_r = __builtin_amdgcn_readfirstlane(qbase_m);                                 \
+        if (PAIRS) {                                                                       \
+            pair_r = pair_m;                                                               \
+            wcb_r = wcb_m;                                                                 \
+            nqvb_r = pair_m ? __builtin_amdgcn_readfirstlane(nqvb_m) : 0;                  \
+            qbaseb_r = __builtin_amdgcn_readfirstlane(qbaseb_m);                           \
+        }                                                                                  \
         if (QP) {                                                                          \
             const int nq_ = qbase_r + nqv_r <= a.row_capacity ? nqv_r : 0;                 \
-            qp8_n = reinterpret_cast<const h16x8 *>(a.qbuf + ((size_t)qbase_r + max(min(la / HP, nq_ - 1), 0)) * QROW)[(head_ok ? hh : 0) * 4 + g]; \
+            const int nb_ = PAIRS && qbaseb_r + nqvb_r <= a.row_capacity ? nqvb_r : 0;     \
+            const int qc_ = max(min(la / HP, nq_ + nb_ - 1), 0);                           \
+            const size_t row_ = nb_ > 0 && qc_ >= nq_ ? (size_t)qbaseb_r + (size_t)(qc_ - nq_) : (size_t)qbase_r + (size_t)qc_; \
+            qp8_n = reinterpret_cast<const h16x8 *>(a.qbuf + row_ * QROW)[(head_ok ? hh : 0) * 4 + g]; \
         }                                                                                  \
         vmask_r = 0; used_r = 0;                                                           \
         _Pragma("unroll") for (int t = 0; t < KT; ++t) {                                   \
             const int r_ = __builtin_bit_cast(int, km_m[t].w);                             \
-            const bool ok_ = 16 * t + la < K && r_ >= 0;                                   \
+            const bool ok_ = (PAIRS && t == 1 && pair_m ? la : 16 * t + la) < K && r_ >= 0; \
             const unsigned long long bal_ = __ballot(ok_);                                 \
             vmask_r |= (unsigned)((bal_ >> (4 * g)) & 15ull) << (4 * t);                   \
             used_r |= (t == 0 || (bal_ & 0xFFFFull) != 0ull) ? 1u << t : 0u;               \
@@ -1161,37 +1200,45 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
             _Pragma("unroll") for (int S = 0; S < NT; ++S) T1n[t][S] = KVH_ROW4(ro_, S);   \
         }                                                                                  \
     }
-    w_p = w_p0;
+    w_p = w_p0; w_pb = w_pb0;
     KVH_LOAD_META()
-    w_p = w_p1;
+    w_p = w_p1; w_pb = w_pb1;
     KVH_ISSUE_ROWS()
     KVH_LOAD_META()
-    w_p = w_p2;
+    w_p = w_p2; w_pb = w_pb2;
     // transposed reads: lane 4 q + p of a 16-lane group addresses row q, columns 4 p .. 4 p + 3 of its 4 x 16 block
     const char *tr_base = Ti + (4 * g + (la >> 2)) * RS + 8 * (la & 3);
     for (; wi < n_act; wi += wstep) {
-        const float4 wc = wc_r;
-        const int nqv = qbase_r + nqv_r <= a.row_capacity ? nqv_r : 0;
-        const size_t qbase = (size_t)qbase_r;
+        const float4 wc = wc_r, wcb = wcb_r;
+        // each window of a pair is clipped against the row capacity on its own; the passes walk both query lists, A's first
+        const int nqa = qbase_r + nqv_r <= a.row_capacity ? nqv_r : 0;
+        const int nqb = PAIRS && qbaseb_r + nqvb_r <= a.row_capacity ? nqvb_r : 0;  // (a single: 0)
+        const int nqv = nqa + nqb;
+        const size_t qbase = (size_t)qbase_r, qbaseb = (size_t)qbaseb_r;
+        const bool pair = PAIRS && pair_r;
         const unsigned vmask = vmask_r, used = used_r;
         // every live key in the first half of the list (wave-uniform): KT = 2 -- in tile 0; KT = 4 -- in its first 32-key step
         const bool front = (used >> (KT / 2)) == 0u;
-        const float ctrb = lane_pick4(g, wc.x, wc.y, wc.z, wc.z);  // wctr is 0 for g = 3
         // key tokens = row + relu(positional MLP), split once, straight into the image (both products read it: the score
         // product row-wise, the second one transposed -- no token registers live across the passes)
         float wu[NT];  // A operand of the positional product: once per window (the window centre), not once per key tile
+        const auto make_wu = [&](const float4 c) __attribute__((always_inline)) {
+            const float ctrb = lane_pick4(g, c.x, c.y, c.z, c.z);  // wctr is 0 for g = 3
 #pragma unroll
-        for (int u = 0; u < NT; ++u) {
-            float cs = wctr[u] * ctrb;
-            cs += lane_xor16(cs);
-            cs += lane_xor32(cs);
-            wu[u] = g == 3 ? wrel[u] + cs : wrel[u];
-        }
+            for (int u = 0; u < NT; ++u) {
+                float cs = wctr[u] * ctrb;
+                cs += lane_xor16(cs);
+                cs += lane_xor32(cs);
+                wu[u] = g == 3 ? wrel[u] + cs : wrel[u];
+            }
+        };
+        make_wu(wc);
 #pragma unroll
         for (int t = 0; t < KT; ++t) {
             // zeros only where a pass body reads them: a dead tile beside a live one in a 32-key step (none at KT = 2,
             // where a dead tile 1 means the `front` body, which reads tile 0 alone)
             if (!(used >> t & 1) && (KT == 2 || (front && t >= KT / 2))) continue;
+            if (PAIRS && t == 1 && pair) make_wu(wcb);  // tile 1 holds window B's keys: its own centre
 #pragma unroll
             for (int P = 0; P < NP; ++P) {
                 h16x8 th = h16x8{0, 0, 0, 0, 0, 0, 0, 0}, tl = th;
@@ -1224,7 +1271,8 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
         }
         KVH_ISSUE_ROWS()
         KVH_LOAD_META()
-        w_p = KVH_WORD(a.perm, min(wi + 3 * wstep, w_last));
+        w_p = KVH_WORD(a.steps, min(wi + 3 * wstep, w_last) * sstr);
+        if (PAIRS) w_pb = KVH_WORD(a.steps, min(wi + 3 * wstep, w_last) * sstr + sstr - 1);
         wave_lds_sync();
         // One pass body per set of live 32-key steps, chosen ONCE per window (`front` is known before its passes start), so
         // that a pass is straight-line code: FRONT -- every live key in the first half of the list.  KT = 2: tile 0 alone
@@ -1236,12 +1284,17 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
         const auto passes = [&](auto front_c) __attribute__((always_inline)) {
             constexpr int LT = decltype(front_c)::value ? KT / 2 : KT, LS = (LT + 1) / 2;  // tiles, 32-key steps this body reads
             for (int q0 = 0; q0 < nqv; q0 += QPP) {
-                const int q = q0 + la / HP;
+                const int q = q0 + la / HP, qc = min(q, nqv - 1);
                 const bool q_ok = q < nqv && head_ok;
-                float *xrow = a.qbuf + (qbase + min(q, nqv - 1)) * QROW + (head_ok ? hh : 0) * CG;
+                // the column's query: A's list first, then B's (a single: nqb = 0)
+                const bool inb = PAIRS && nqb > 0 && qc >= nqa;
+                const size_t qrow_i = inb ? qbaseb + (size_t)(qc - nqa) : qbase + (size_t)qc;
+                float *xrow = a.qbuf + qrow_i * QROW + (head_ok ? hh : 0) * CG;
+                // a pair's column keeps its own window's tile (bits 4 t .. 4 t + 3 of vmask: tile t)
+                const unsigned vmq = pair ? (inb ? vmask & 0xF0u : vmask & 0x0Fu) : vmask;
                 if (q0 > 0) {
                     if (QP) {
-                        qp8 = reinterpret_cast<const h16x8 *>(a.qbuf + (qbase + min(q, nqv - 1)) * QROW)[(head_ok ? hh : 0) * 4 + g];
+                        qp8 = reinterpret_cast<const h16x8 *>(a.qbuf + qrow_i * QROW)[(head_ok ? hh : 0) * 4 + g];
                     } else {
                         const h16x8 *qrow = reinterpret_cast<const h16x8 *>(xrow);
 #pragma unroll
@@ -1304,7 +1357,7 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const float sv = QP ? sc[t][i] : sc[t][i] * 1.4426950408889634f;
-                        sc[t][i] = (vmask >> (4 * t + i) & 1) ? sv : -INFINITY;
+                        sc[t][i] = (vmq >> (4 * t + i) & 1) ? sv : -INFINITY;
                         mx = fmaxf(mx, sc[t][i]);
                     }
                 mx = fmaxf(mx, lane_xor16(mx));
@@ -1367,7 +1420,7 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
 }
 
 template <int CG, int HD, int HP>
-static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, bool kv16, hipStream_t stream) {
+static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, bool kv16, bool paired, hipStream_t stream) {
     constexpr int CGP = (CG + 15) / 16 * 16, LS = CGP + 4;
     int dev = 0, cus = 256;
     if (hipGetDevice(&dev) == hipSuccess &&
@@ -1396,6 +1449,7 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
             if (grid16 < 1) grid16 = 1;
             // packed weights: A and C as k_attn_q16 / k_attn_o16, and at K <= 32 the Q' hand-off (Qt formed in the window launch)
             const bool qp = packed && K <= 32;
+            if (paired && !(qp && HD == 16)) return MSSVT_E_TOOLARGE;  // only k_attn_kvh<.., 2, true> walks step pairs
             if constexpr (HD == 16) {
                 if (qp) {
                     using L = AttnBlob<CG>;
@@ -1428,6 +1482,7 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
             return mssvt_launch_status();
         }
     }
+    if (paired) return MSSVT_E_TOOLARGE;
     k_attn_q<CG, HD, HP, false><<<dim3(row_grid, ng), ATTN_QO_WAVES * MSSVT_WAVE, lds_q, stream>>>(pack);
     // B: persistent over the work order with exactly the waves that are resident (3 workgroups of 4 waves per CU at the
     // 164 VGPRs of the K = 32 instantiation): every further workgroup would run in a later round and pay the prologue
@@ -1452,10 +1507,10 @@ static int launch_block_attn(const AttnPack &pack, int ng, int row_capacity, boo
     return mssvt_launch_status();
 }
 
-static int dispatch_block_attn(const AttnPack &pack, int ng, int Cg, int head_dim, int row_capacity, bool kv16, hipStream_t st) {
+static int dispatch_block_attn(const AttnPack &pack, int ng, int Cg, int head_dim, int row_capacity, bool kv16, bool paired, hipStream_t st) {
 #define MSSVT_ATTN_CASE(cg, hd)                                   \
     if (Cg == cg && head_dim == hd)                               \
-        return launch_block_attn<cg, hd, ((cg / hd + 3) / 4) * 4>(pack, ng, row_capacity, kv16, st);
+        return launch_block_attn<cg, hd, ((cg / hd + 3) / 4) * 4>(pack, ng, row_capacity, kv16, paired, st);
     MSSVT_ATTN_CASE(8, 8)
     MSSVT_ATTN_CASE(16, 8)
     MSSVT_ATTN_CASE(16, 16)
@@ -1478,7 +1533,8 @@ static int block_attention_impl(
     const float *const *host_kmeta, const float *wcentre, const float *const *host_Wq, const float *const *host_bq,
     const float *const *host_Wkv, const float *const *host_bkv, const float *const *host_Wo,
     const float *const *host_bo, const float *Wpos, const float *bpos, float *qbuf, float *attn, bool kv16,
-    const void *const *host_packed, void *stream) {
+    const void *const *host_packed, const int *const *host_steps, const int *const *host_num_steps, void *stream) {
+    if ((host_steps == nullptr) != (host_num_steps == nullptr)) return MSSVT_E_BADARG;
     if (!host_c0 || !host_cg || !host_heads || !xhat || !num_active_dev || !perm || !q_off || !nq_valid ||
         !num_rows_dev || !qrow_meta || !qrow_src || !host_kmeta || !wcentre || !host_Wq || !host_bq || !host_Wkv ||
         !host_bkv || !host_Wo || !host_bo || !Wpos || !bpos || !qbuf || !attn || C <= 0 || num_groups <= 0 ||
@@ -1496,6 +1552,7 @@ static int block_attention_impl(
         const int c0 = host_c0[g], Cg = host_cg[g], heads = host_heads[g];
         if (!host_kmeta[g] || !host_Wq[g] || !host_bq[g] || !host_Wkv[g] || !host_bkv[g] || !host_Wo[g] || !host_bo[g])
             return MSSVT_E_BADARG;
+        if (host_steps && (!host_steps[g] || !host_num_steps[g])) return MSSVT_E_BADARG;
         if (Cg <= 0 || heads <= 0 || Cg != heads * head_dim || c0 < 0 || c0 + Cg > C || (c0 & 3)) return MSSVT_E_BADARG;
         // one channel per lane, <= 8 heads per group
         if (Cg > MSSVT_WAVE || heads > 8) return MSSVT_E_TOOLARGE;
@@ -1504,6 +1561,9 @@ static int block_attention_impl(
         a.nq = nq; a.K = key_num_sample;
         a.xhat = xhat; a.num_wins = num_active_dev; a.perm = perm; a.q_off = q_off; a.nq_valid = nq_valid;
         a.num_rows = num_rows_dev;
+        a.steps = host_steps ? host_steps[g] : perm;
+        a.num_steps = host_steps ? host_num_steps[g] : num_active_dev;
+        a.step_stride = host_steps ? 2 : 1;
         a.qrow_meta = reinterpret_cast<const float4 *>(qrow_meta);
         a.qrow_src = reinterpret_cast<const int2 *>(qrow_src);
         a.kmeta = reinterpret_cast<const float4 *>(host_kmeta[g]);
@@ -1518,15 +1578,16 @@ static int block_attention_impl(
         if (same) {
             pack.g[g] = a;
         } else {  // unequal group widths: one launch triple per group
+            if (host_steps) return MSSVT_E_TOOLARGE;
             AttnPack one;
             for (int i = 0; i < ATTN_MAX_GROUPS; ++i) one.g[i] = a;
-            const int rc = dispatch_block_attn(one, 1, Cg, head_dim, row_capacity, kv16, st);
+            const int rc = dispatch_block_attn(one, 1, Cg, head_dim, row_capacity, kv16, false, st);
             if (rc) return rc;
         }
     }
     if (!same) return MSSVT_OK;
     for (int g = num_groups; g < ATTN_MAX_GROUPS; ++g) pack.g[g] = pack.g[0];
-    return dispatch_block_attn(pack, num_groups, host_cg[0], head_dim, row_capacity, kv16, st);
+    return dispatch_block_attn(pack, num_groups, host_cg[0], head_dim, row_capacity, kv16, host_steps != nullptr, st);
 }
 
 #define ATTN_ENTRY_PARAMS                                                                                              \
@@ -1540,7 +1601,7 @@ static int block_attention_impl(
     C, num_groups, host_c0, host_cg, host_heads, head_dim, scale, nq, key_num_sample, xhat, num_active_dev, perm,      \
     q_off, nq_valid, num_rows_dev, row_capacity, qrow_meta, qrow_src, host_kmeta, wcentre, host_Wq, host_bq, host_Wkv, \
     host_bkv, host_Wo, host_bo, Wpos, bpos, qbuf, attn
-extern "C" int mssvt_block_attention(ATTN_ENTRY_PARAMS) { return block_attention_impl(ATTN_ENTRY_ARGS, false, nullptr, stream); }
+extern "C" int mssvt_block_attention(ATTN_ENTRY_PARAMS) { return block_attention_impl(ATTN_ENTRY_ARGS, false, nullptr, nullptr, nullptr, stream); }
 // launch B with split-fp16 matrix operands (k_attn_kvh) where the shape allows (Cg % 32 == 0, 16 < K <= 64), the fp32
 // form otherwise; with host_packed (one mssvt_attn_pack_weights blob per group; head_dim 16) launches A and C run on the
 // pre-split fragments too.  The CALLER guarantees the fp16 range of key tokens, Q', Qt, Xbar and V
@@ -1552,7 +1613,21 @@ extern "C" int mssvt_block_attention_kv16(
     const float *const *host_Wkv, const float *const *host_bkv, const float *const *host_Wo,
     const float *const *host_bo, const float *Wpos, const float *bpos, float *qbuf, float *attn,
     const void *const *host_packed, void *stream) {
-    return block_attention_impl(ATTN_ENTRY_ARGS, true, host_packed, stream);
+    return block_attention_impl(ATTN_ENTRY_ARGS, true, host_packed, nullptr, nullptr, stream);
+}
+// mssvt_block_attention_kv16 whose window launch walks one step list per head group (mssvt_plan_order_steps): two one-tile
+// windows per wavefront step.  Only the Q' hand-off form takes pairs (blobs, head_dim 16, key_num_sample <= 32, equal group
+// widths): MSSVT_E_TOOLARGE for every other launch form, before anything is launched.
+extern "C" int mssvt_block_attention_kv16_steps(
+    int C, int num_groups, const int *host_c0, const int *host_cg, const int *host_heads, int head_dim, float scale,
+    int nq, int key_num_sample, const float *xhat, const int *num_active_dev, const int *perm, const int *q_off,
+    const int *nq_valid, const int *num_rows_dev, int row_capacity, const float *qrow_meta, const int *qrow_src,
+    const float *const *host_kmeta, const float *wcentre, const float *const *host_Wq, const float *const *host_bq,
+    const float *const *host_Wkv, const float *const *host_bkv, const float *const *host_Wo,
+    const float *const *host_bo, const float *Wpos, const float *bpos, float *qbuf, float *attn,
+    const void *const *host_packed, const int *const *host_steps, const int *const *host_num_steps, void *stream) {
+    if (!host_packed || !host_steps || !host_num_steps) return MSSVT_E_BADARG;
+    return block_attention_impl(ATTN_ENTRY_ARGS, true, host_packed, host_steps, host_num_steps, stream);
 }
 
 extern "C" long long mssvt_attn_packed_bytes(int Cg, int head_dim) {

@@ -9,7 +9,7 @@
 //
 //     fill (-1 arena, zero region, the output table) + the first norm1 in the same launch    k_frame_fill_ln
 //     level set-up of the (b,x,y,z)-sorted input list + early device-to-host copy            mssvt_level_setup_sorted_pillars
-//     window plan of the two-scale Blocks                                                    mssvt_window_plan_two_vox
+//     window plan of the two-scale Blocks (+ the upper-tile flags of the paired window launch)  mssvt_window_plan_two_vox / _live
 //     work orders; in the launch of their query rows, the interpolation tables per voxel
 //     and the CompressBlock's chunk ends                                                     mssvt_plan_order_multi_vt (voxel_tables.hip.h)
 //     per Block: window attention, FFN tail (emits the next block's norm1)                   mssvt_block_attention*, mssvt_ffn_fused_interp
@@ -181,6 +181,9 @@ struct Layout {
     int n_tabs, tab_pat[4], tab_interp[4];
     int n_pat, pats[3];
     int *perm[3], *n_act[3], *q_off[3], *row_src[3], *n_rows[3];
+    // step lists of the paired window launch, per (pattern, head group), and the plan's upper-tile flags per group
+    bool paired;
+    int *live[2], *steps[6], *n_steps[6], *step_scratch;
     float *row_meta[3];
     long long row_cap;
     float *qbuf, *attn[3];
@@ -190,6 +193,13 @@ struct Layout {
     float *c_qp, *c_ktok, *c_score, *c_vp, *c_new;
     size_t total;
 };
+
+// A Block whose window launch is the K <= 32 Q' hand-off form (k_attn_kvh<.., 2, true>: packed weights, head_dim 16, one launch
+// for the two equal head groups): it walks step lists, two one-tile windows to a step (mssvt_block_attention_kv16_steps)
+bool block_pairs(const Frame &f, const FrBlock &k) {
+    return k.attn_mode == 1 && k.have_packed && k.head_dim == 16 && f.plan.K > 16 && f.plan.K <= 32 && k.ng == 2 &&
+           k.cg[0] == k.cg[1] && (k.cg[0] == 32 || k.cg[0] == 64);
+}
 
 int pattern_slot(const Layout &L, int pattern) {
     for (int i = 0; i < L.n_pat; ++i)
@@ -274,6 +284,15 @@ void make_layout(const Frame &f, int n, char *base, Layout &L) {
         L.row_src[i] = b.take<int>((size_t)L.row_cap * 2);
         L.n_rows[i] = b.take<int>(1);
     }
+    L.paired = false;
+    for (const FrBlock &k : f.blocks) L.paired = L.paired || (L.vox_tables && block_pairs(f, k));
+    for (int g = 0; g < 2; ++g) L.live[g] = L.paired ? b.take<int>(cap) : nullptr;
+    for (int i = 0; i < 6; ++i) {
+        const bool on = L.paired && i < 2 * L.n_pat;
+        L.steps[i] = on ? b.take<int>(2 * cap) : nullptr;
+        L.n_steps[i] = on ? b.take<int>(1) : nullptr;
+    }
+    L.step_scratch = L.paired ? b.take<int>((size_t)mssvt_plan_order_steps_scratch_ints(L.n_pat, 2)) : nullptr;
     // hand-off scratch of the attention launches: one row per valid query, one region per head group
     size_t qwidth = 0;
     if (!f.blocks.empty())
@@ -587,7 +606,14 @@ extern "C" int mssvt_frame_forward(void *frame, int num_voxels, const float *fea
         tab_row[t] = L.tab_rows + (size_t)t * n * 4;
         tab_w[t] = L.tab_w + (size_t)t * n * 4;
     }
-    if (L.vox_tables) {
+    if (L.paired) {
+        FR_TRY_FORKED(mssvt_window_plan_two_live(
+            X, Y, Z, p.ws[0], p.ws[1], p.ws[2], p.n_o, p.n_e, p.n1, p.n2, H, B, p.num_o, p.num_e, p.num_1, p.num_2, p.t_o, p.t_e,
+            p.t_1, p.t_2, p.K, L.win_blk, L.hdr[0] + 1, cap, nullptr, L.cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+            nullptr, L.win_vstart, nullptr, nullptr, nullptr, indices, f->vs, mn3, wsm, L.qmeta[0], L.qmeta[1], L.qmeta[2],
+            L.kmeta[0], L.kmeta[1], L.wcentre, L.nq_valid, L.occ, p.fp4, p.packed_offsets, L.vbase, L.status, L.vcount_blk,
+            L.vox_win, L.live[0], L.live[1], stream));
+    } else if (L.vox_tables) {
         FR_TRY_FORKED(mssvt_window_plan_two_vox(
             X, Y, Z, p.ws[0], p.ws[1], p.ws[2], p.n_o, p.n_e, p.n1, p.n2, H, B, p.num_o, p.num_e, p.num_1, p.num_2, p.t_o, p.t_e,
             p.t_1, p.t_2, p.K, L.win_blk, L.hdr[0] + 1, cap, nullptr, L.cnt, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
@@ -623,8 +649,11 @@ extern "C" int mssvt_frame_forward(void *frame, int num_voxels, const float *fea
             FR_TRY_FORKED(vt_make_args(vt, n, indices, L.vox_win, L.nq_valid, cap, L.qmeta[0], L.qmeta[1], L.qmeta[2], p.n_o, p.n_e, p.n1,
                                        f->vs, mn3, L.vox_tables ? L.n_tabs : 0, tab_list, L.tab_interp, tab_zero, tab_row, tab_w,
                                        L.c_groups, L.hdr[1] + 1, L.pair_win, L.c_ends));
+        // ---- the step lists of the paired window launches: further workgroups of the same k_plan_order launches
+        const PlanStepsArgs sa{2, L.live, L.steps, L.n_steps, L.step_scratch};
         FR_TRY_FORKED(mssvt_plan_order_multi_vt(L.n_pat, L.hdr[0] + 1, nqv, nq, qm, cap, (int)L.row_cap, L.perm, L.n_act, L.q_off,
-                                                L.row_meta, L.row_src, L.n_rows, ride ? &vt : nullptr, stream));
+                                                L.row_meta, L.row_src, L.n_rows, ride ? &vt : nullptr, L.paired ? &sa : nullptr,
+                                                stream));
     }
     if (f->overlap) {
         const hipError_t e = hipStreamWaitEvent(stream, f->join, 0);
@@ -644,6 +673,11 @@ extern "C" int mssvt_frame_forward(void *frame, int num_voxels, const float *fea
             FR_TRY(mssvt_block_attention_bf16(C, k.ng, k.c0, k.cg, k.heads, k.head_dim, k.scale, nq, p.K, xhat, L.n_act[s], L.perm[s],
                                               L.q_off[s], nqv, L.n_rows[s], (int)L.row_cap, L.row_meta[s], L.row_src[s], kmeta,
                                               L.wcentre, k.Wq, k.bq, k.Wkv, k.bkv, k.Wo, k.bo, k.Wp, k.bp, L.attn[s], stream));
+        } else if (L.paired && block_pairs(*f, k)) {
+            FR_TRY(mssvt_block_attention_kv16_steps(C, k.ng, k.c0, k.cg, k.heads, k.head_dim, k.scale, nq, p.K, xhat, L.n_act[s],
+                                                    L.perm[s], L.q_off[s], nqv, L.n_rows[s], (int)L.row_cap, L.row_meta[s], L.row_src[s],
+                                                    kmeta, L.wcentre, k.Wq, k.bq, k.Wkv, k.bkv, k.Wo, k.bo, k.Wp, k.bp, L.qbuf,
+                                                    L.attn[s], k.packed, L.steps + 2 * s, L.n_steps + 2 * s, stream));
         } else if (k.attn_mode == 1) {
             FR_TRY(mssvt_block_attention_kv16(C, k.ng, k.c0, k.cg, k.heads, k.head_dim, k.scale, nq, p.K, xhat, L.n_act[s], L.perm[s],
                                               L.q_off[s], nqv, L.n_rows[s], (int)L.row_cap, L.row_meta[s], L.row_src[s], kmeta,

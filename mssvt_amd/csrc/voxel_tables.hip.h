@@ -172,8 +172,20 @@ int vt_make_args(VtArgs &a, int num_voxels, const int *indices, const int *vox_w
                  float *const *host_tab_w, int chunk_groups, const int *chunk_num_wins_dev, const int *chunk_pair_win,
                  int *chunk_ends);
 
-// mssvt_plan_order_multi (window_plan.hip) whose k_query_rows launch also carries the workgroups of `vt` (NULL: none)
+// step lists of the paired window launch, built by the plan-order launches (window_plan.hip, mssvt_plan_order_steps):
+// live[g] = the plan kernel's flag of head group g, steps / num_steps[list * num_groups + g], scratch of
+// mssvt_plan_order_steps_scratch_ints ints
+struct PlanStepsArgs {
+    int num_groups;
+    const int *const *live;
+    int *const *steps, *const *num_steps;
+    int *scratch;
+};
+
+// mssvt_plan_order_multi (window_plan.hip) whose k_query_rows launch also carries the workgroups of `vt` (NULL: none) and whose
+// k_plan_order launches also build the step lists of `sa` (NULL: none)
 int mssvt_plan_order_multi_vt(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid, const int *host_nq,
                               const float *const *host_qmeta, int win_capacity, int row_capacity, int *const *host_perm,
                               int *const *host_num_active, int *const *host_q_off, float *const *host_qrow_meta,
-                              int *const *host_qrow_src, int *const *host_num_rows, const VtArgs *vt, void *stream);
+                              int *const *host_qrow_src, int *const *host_num_rows, const VtArgs *vt, const PlanStepsArgs *sa,
+                              void *stream);

@@ -70,6 +70,9 @@ struct PlanArgs {
     // optional (mssvt_window_plan_two_vox): per voxel of a win1 list the window that lists it, for the per-voxel table
     // kernel (voxel_tables.hip) -- then no table is built here
     int *vox_win;
+    // optional (mssvt_window_plan_two_live): per window and key scale, 1 when a slot 16 .. K-1 of its key list holds a row
+    // (the window then needs the upper key tile of k_attn_kvh and cannot share a step), else 0
+    int *live1, *live2;
     struct PlanTab {
         int list, maxn, interp, zero_row;  // list: 0 odd, 1 even, 2 win1 (the queries); zero_row: attention row of zeros
         int4 *tab_row;
@@ -623,6 +626,8 @@ __global__ void __launch_bounds__(PLAN_MAX_WPB *MSSVT_WAVE, FPS_TPL <= 4 ? PLAN_
         unsigned char *mout0 = scale ? a.k_mask2 : a.k_mask1;
         int *kout = kout0 ? kout0 + (size_t)w * K : nullptr;
         unsigned char *mout = mout0 ? mout0 + (size_t)w * K : nullptr;
+        int *const live_out = scale ? a.live2 : a.live1;
+        unsigned long long upper = 0ull;
         for (int j = lane; j < K; j += MSSVT_WAVE) {
             const int f = fps_out[j];
             const bool entry = f < nv;  // a list entry (else an empty slot: index -1, offset (0,0,0))
@@ -632,6 +637,7 @@ __global__ void __launch_bounds__(PLAN_MAX_WPB *MSSVT_WAVE, FPS_TPL <= 4 ? PLAN_
             if (kout) kout[j] = kid;
             const bool masked = (j > 0 && f == 0) || kid < 0;
             if (mout) mout[j] = (unsigned char)(masked ? 1 : 0);
+            if (live_out) upper |= __ballot(!masked && j >= 16);
             if (a.kmeta1) {
                 float4 m = none;
                 if (!masked) {
@@ -652,6 +658,7 @@ __global__ void __launch_bounds__(PLAN_MAX_WPB *MSSVT_WAVE, FPS_TPL <= 4 ? PLAN_
                 (scale ? a.kmeta2 : a.kmeta1)[(size_t)w * K + j] = m;
             }
         }
+        if (live_out && lane == 0) live_out[w] = upper != 0ull ? 1 : 0;
         wave_lds_sync();
         PSTAMP()
     }
@@ -681,7 +688,8 @@ static int plan_two_launch(
     float *kmeta2, float *wcentre, int *nq_valid, const unsigned long long *occ_columns,
     const int *host_footprint4, const int *packed_offsets, const int *column_vbase, const int *level_status_dev,
     const int *win_counts_dev, int num_tabs, const int *host_tab_list, const int *host_tab_interp,
-    const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w, int *vox_win, void *stream) {
+    const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w, int *vox_win, int *live1, int *live2,
+    void *stream) {
     // (ind_* / k_ind* / k_mask* / owner_*: each optional when the resolved metadata is asked for -- the fused consumers read
     // kmeta / qmeta / the tables; without metadata they are the call's only outputs)
     const bool lists_wanted = ind_odd && ind_even && ind_win1 && k_ind1 && k_ind2 && k_mask1 && k_mask2 && owner_win1 && owner_odd && owner_even;
@@ -744,6 +752,8 @@ static int plan_two_launch(
     a.n_tabs = 0;
     a.tab_q = 0;
     a.vox_win = vox_win;
+    a.live1 = live1; a.live2 = live2;
+    if ((live1 == nullptr) != (live2 == nullptr) || (live1 && !kmeta1)) return MSSVT_E_BADARG;
     if (vox_win && (num_tabs != 0 || !kmeta1)) return MSSVT_E_BADARG;
     if (num_tabs < 0 || num_tabs > 4) return MSSVT_E_TOOLARGE;
     if (num_tabs > 0) {
@@ -844,7 +854,7 @@ extern "C" int mssvt_window_plan_two(PLAN_TWO_PARAMS, int num_tabs, const int *h
                                      const int *host_tab_zero_row, int *const *host_tab_row, float *const *host_tab_w,
                                      void *stream) {
     return plan_two_launch(PLAN_TWO_ARGS, num_tabs, host_tab_list, host_tab_interp, host_tab_zero_row, host_tab_row, host_tab_w,
-                           nullptr, stream);
+                           nullptr, nullptr, nullptr, stream);
 }
 
 // The same plan without tables: vox_win (N ints, pre-filled with -1) receives, for every voxel of a win1 list, the window
@@ -854,7 +864,15 @@ extern "C" int mssvt_window_plan_two(PLAN_TWO_PARAMS, int num_tabs, const int *h
 extern "C" int mssvt_window_plan_two_vox(PLAN_TWO_PARAMS, int *vox_win, void *stream) {
     if (!vox_win || !kmeta1) return MSSVT_E_BADARG;
     if (max_num_odd > max_num_win1 || num_odd + max_num_even > max_num_win1) return MSSVT_E_TOOLARGE;
-    return plan_two_launch(PLAN_TWO_ARGS, 0, nullptr, nullptr, nullptr, nullptr, nullptr, vox_win, stream);
+    return plan_two_launch(PLAN_TWO_ARGS, 0, nullptr, nullptr, nullptr, nullptr, nullptr, vox_win, nullptr, nullptr, stream);
+}
+
+// mssvt_window_plan_two_vox that also leaves, per window and key scale, whether the key list has a row in a slot 16 .. K-1
+// (live1 / live2: win_capacity ints, written for every window below *num_wins_dev; every other output as without them)
+extern "C" int mssvt_window_plan_two_live(PLAN_TWO_PARAMS, int *vox_win, int *live1, int *live2, void *stream) {
+    if (!vox_win || !kmeta1 || !live1 || !live2) return MSSVT_E_BADARG;
+    if (max_num_odd > max_num_win1 || num_odd + max_num_even > max_num_win1) return MSSVT_E_TOOLARGE;
+    return plan_two_launch(PLAN_TWO_ARGS, 0, nullptr, nullptr, nullptr, nullptr, nullptr, vox_win, live1, live2, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -900,8 +918,11 @@ int mssvt_occupancy_columns_launch(const int *indices, int num_voxels, int batch
 // ---------------------------------------------------------------------------------------------
 #define PO_WAVES 16
 #define PO_KEYS 257
+#define PO_SKEYS 515  // step lists: key = 2 min(nq_valid, 256) + (upper key tile live); odd, as PO_KEYS (LDS banks)
 #define PO_V 8  // window batches of 64 in flight per wave (one global-load latency per PO_V batches)
 #define PO_MAX_SETS 4
+#define PO_STEP_SCRATCH (64 * (PO_SKEYS + 1))  // ints per step list: the histograms of up to 64 workgroups
+#define PO_MAX_ROWS 12  // grid.y: the query lists, then one step list per (query list, head group)
 struct PlanOrderSet {
     const int *nq_valid;
     int max_key, nq;
@@ -909,9 +930,14 @@ struct PlanOrderSet {
     int *perm, *num_active, *q_off, *num_rows;
     float4 *rmeta;
     int2 *rsrc;
+    // a step-list row (steps != null; mssvt_plan_order_steps): nq_valid / max_key as the query list's, `live` = the plan
+    // kernel's flag of one head group (1: the window needs the upper key tile), steps = 2 ints per step, scratch = G x
+    // (PO_SKEYS + 1) ints of its own.  The row writes steps / num_steps only.
+    const int *live;
+    int *steps, *num_steps, *scratch;
 };
 struct PlanOrderPack {
-    PlanOrderSet s[PO_MAX_SETS];
+    PlanOrderSet s[PO_MAX_ROWS];
 };
 
 // blockIdx.y = query list (the lists of a plan are ordered in one launch), blockIdx.x = one of G workgroups that
@@ -919,24 +945,30 @@ struct PlanOrderPack {
 // `scratch` (G x (PO_KEYS + 1) ints, the head of the list's row array that k_query_rows only fills afterwards),
 // PHASE 1 turns the other workgroups' histograms into its offsets and then sorts its own run exactly like the
 // single workgroup does.  G == 1: PHASE 1 alone.
-template <int PHASE>
-__global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *num_wins, int row_capacity,
-                                                                     PlanOrderPack pack) {
-    const PlanOrderSet &ps = pack.s[blockIdx.y];
+// STEPS: the same counting sort on the key (query count, upper tile live) emits the work list of k_attn_kvh's paired
+// form instead of perm: a step is (wA, wB).  The windows of a one-tile sub-bucket (flag clear) go two to a step -- rank p
+// to slot p & 1 of step base + p / 2, the last of an odd sub-bucket alone with wB = -1; every other window is a step
+// (w, -1).  Steps are in the order of perm's buckets (descending query count; within a count the flagged windows first).
+template <int PHASE, bool STEPS>
+__device__ __forceinline__ void plan_order_body(const PlanOrderSet &ps, const int *num_wins, int row_capacity) {
+    constexpr int NK = STEPS ? PO_SKEYS : PO_KEYS, KPL = STEPS ? 8 : 4, KMIN = STEPS ? 2 : 1;  // (KPL x 64 keys from the top)
     const int *nq_valid = ps.nq_valid;
+    const int *live = ps.live;
     const int max_key = ps.max_key;
+    const int top_key = STEPS ? 2 * max_key + 1 : max_key;
     const int G = gridDim.x, gidx = blockIdx.x;
-    int *scratch = reinterpret_cast<int *>(ps.rsrc);
+    int *scratch = STEPS ? ps.scratch : reinterpret_cast<int *>(ps.rsrc);
     int *perm = ps.perm, *num_active = ps.num_active, *q_off = ps.q_off, *num_rows = ps.num_rows;
-    // per-wave histograms: copies sit PO_KEYS (odd) words apart -> different LDS banks, so the 16
+    // per-wave histograms: copies sit NK (odd) words apart -> different LDS banks, so the 16
     // waves' atomics on the few populated keys proceed in parallel
-    __shared__ int hist[PO_WAVES][PO_KEYS];
-    __shared__ int key_base[PO_KEYS];
+    __shared__ int hist[PO_WAVES][NK];
+    __shared__ int key_base[NK];
+    __shared__ int key_cnt[STEPS ? NK : 1];  // (STEPS) windows per key, all workgroups: the last of an odd sub-bucket is alone
     __shared__ int wave_q[PO_WAVES];
     __shared__ int rows_before, rows_all;
     const int nw = *num_wins;
     const int wv = threadIdx.x / MSSVT_WAVE, lane = lane_id();
-    for (int k = threadIdx.x; k < PO_WAVES * PO_KEYS; k += blockDim.x) (&hist[0][0])[k] = 0;
+    for (int k = lane; k <= top_key; k += MSSVT_WAVE) hist[wv][k] = 0;  // (each wave its own copy, the keys in use only)
     __syncthreads();
     // each workgroup, and inside it each wave, owns a contiguous run of windows
     const int per_wg = (nw + G - 1) / G;
@@ -946,16 +978,17 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
     // pass 0: histogram of the query counts + the run's total
     int total = 0;
     for (int base = wb; base < we; base += MSSVT_WAVE * PO_V) {
-        int v[PO_V];
+        int v[PO_V], fl[PO_V];
 #pragma unroll
         for (int u = 0; u < PO_V; ++u) {
             const int w = base + u * MSSVT_WAVE + lane;
             v[u] = w < we ? nq_valid[w] : -1;
+            fl[u] = STEPS && w < we ? live[w] : 0;
         }
 #pragma unroll
         for (int u = 0; u < PO_V; ++u)
             if (v[u] >= 0) {
-                atomicAdd(&hist[wv][min(v[u], max_key)], 1);
+                atomicAdd(&hist[wv][STEPS ? 2 * min(v[u], max_key) + (fl[u] != 0 ? 1 : 0) : min(v[u], max_key)], 1);
                 total += v[u];
             }
     }
@@ -963,27 +996,27 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
     if (lane == 0) wave_q[wv] = total;
     __syncthreads();
     if (PHASE == 0) {  // publish this workgroup's histogram and row total
-        if (threadIdx.x <= max_key) {
+        if (threadIdx.x <= top_key) {
             int c = 0;
             for (int i = 0; i < PO_WAVES; ++i) c += hist[i][threadIdx.x];
-            scratch[gidx * (PO_KEYS + 1) + threadIdx.x] = c;
+            scratch[gidx * (NK + 1) + threadIdx.x] = c;
         }
         if (threadIdx.x == 0) {
             int rows = 0;
             for (int i = 0; i < PO_WAVES; ++i) rows += wave_q[i];
-            scratch[gidx * (PO_KEYS + 1) + PO_KEYS] = rows;
+            scratch[gidx * (NK + 1) + NK] = rows;
         }
         return;
     }
     // hist[wv][k] -> exclusive prefix over the earlier workgroups and the waves, key totals -> key_base
     // (heaviest key first)
-    if (threadIdx.x <= max_key) {
+    if (threadIdx.x <= top_key) {
         int run = 0, all = 0;
         // (8 requests in flight: one by one the other workgroups' counts were G <= 64 dependent L2 round trips, most of this launch)
         for (int g0 = 0; g0 < G && G > 1; g0 += 8) {
             int c[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) c[u] = g0 + u < G ? scratch[(g0 + u) * (PO_KEYS + 1) + threadIdx.x] : 0;
+            for (int u = 0; u < 8; ++u) c[u] = g0 + u < G ? scratch[(g0 + u) * (NK + 1) + threadIdx.x] : 0;
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 run += g0 + u < gidx ? c[u] : 0;
@@ -998,13 +1031,14 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
             own += c;
         }
         key_base[threadIdx.x] = G > 1 ? all : own;
+        if (STEPS) key_cnt[threadIdx.x] = G > 1 ? all : own;
     }
     if (threadIdx.x == PO_WAVES * MSSVT_WAVE - 1) {
         int before = 0, all = 0;
         for (int g0 = 0; g0 < G && G > 1; g0 += 8) {
             int c[8];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) c[u] = g0 + u < G ? scratch[(g0 + u) * (PO_KEYS + 1) + PO_KEYS] : 0;
+            for (int u = 0; u < 8; ++u) c[u] = g0 + u < G ? scratch[(g0 + u) * (NK + 1) + NK] : 0;
 #pragma unroll
             for (int u = 0; u < 8; ++u) {
                 before += g0 + u < gidx ? c[u] : 0;
@@ -1020,12 +1054,14 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
     if (wv == 0) {
         // key_base[k] = windows with more queries than k (heaviest key first): a descending exclusive prefix, 4 keys per
         // lane + one wave scan instead of one thread walking up to 256 keys (PO_KEYS <= 4 x 64 + 1; key 0 -- windows
-        // without a query -- is not placed)
-        int c[4], sum = 0;
+        // without a query -- is not placed).  STEPS: 8 keys per lane, and a one-tile sub-bucket (even key) counts its
+        // steps, ceil(windows / 2)
+        int c[KPL], sum = 0;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = max_key - (4 * lane + j);
-            c[j] = k >= 1 ? key_base[k] : 0;
+        for (int j = 0; j < KPL; ++j) {
+            const int k = top_key - (KPL * lane + j);
+            c[j] = k >= KMIN ? key_base[k] : 0;
+            if (STEPS && (k & 1) == 0) c[j] = (c[j] + 1) >> 1;
             sum += c[j];
         }
         int incl = sum;
@@ -1035,18 +1071,48 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
         }
         int run = incl - sum;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int k = max_key - (4 * lane + j);
-            if (k >= 1) key_base[k] = run;
+        for (int j = 0; j < KPL; ++j) {
+            const int k = top_key - (KPL * lane + j);
+            if (k >= KMIN) key_base[k] = run;
             run += c[j];
         }
         if (gidx == 0 && lane == MSSVT_WAVE - 1) {
-            *num_active = incl;
-            // past the capacity (caller's bound) pass 1 leaves the first row of the first window that does not fit
-            if (rows_all <= row_capacity) *num_rows = rows_all;
+            if (STEPS) {
+                *ps.num_steps = incl;
+            } else {
+                *num_active = incl;
+                // past the capacity (caller's bound) pass 1 leaves the first row of the first window that does not fit
+                if (rows_all <= row_capacity) *num_rows = rows_all;
+            }
         }
     }
     __syncthreads();
+    if (STEPS) {  // pass 1: the steps
+        int2 *steps = reinterpret_cast<int2 *>(ps.steps);
+        for (int base = wb; base < we; base += MSSVT_WAVE * PO_V) {
+            int v[PO_V], fl[PO_V];
+#pragma unroll
+            for (int u = 0; u < PO_V; ++u) {
+                const int w = base + u * MSSVT_WAVE + lane;
+                v[u] = w < we ? nq_valid[w] : -1;
+                fl[u] = w < we ? live[w] : 0;
+            }
+#pragma unroll
+            for (int u = 0; u < PO_V; ++u) {
+                const int w = base + u * MSSVT_WAVE + lane;
+                if (v[u] <= 0) continue;
+                const int k = 2 * min(v[u], max_key) + (fl[u] != 0 ? 1 : 0);
+                const int p = atomicAdd(&hist[wv][k], 1);  // rank in the sub-bucket, all workgroups
+                if (k & 1)
+                    steps[key_base[k] + p] = make_int2(w, -1);
+                else if (p == key_cnt[k] - 1 && !(p & 1))
+                    steps[key_base[k] + (p >> 1)] = make_int2(w, -1);
+                else
+                    ps.steps[2 * (key_base[k] + (p >> 1)) + (p & 1)] = w;
+            }
+        }
+        return;
+    }
     // pass 1: q_off = exclusive scan of nq_valid in window order; perm = counting sort
     int carry = rows_before;
     for (int i = 0; i < wv; ++i) carry += wave_q[i];
@@ -1079,6 +1145,16 @@ __global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *
             carry += __shfl(incl, MSSVT_WAVE - 1);
         }
     }
+}
+
+template <int PHASE>
+__global__ void __launch_bounds__(PO_WAVES *MSSVT_WAVE) k_plan_order(const int *num_wins, int row_capacity,
+                                                                     PlanOrderPack pack) {
+    const PlanOrderSet &ps = pack.s[blockIdx.y];
+    if (ps.steps)  // (workgroup-uniform)
+        plan_order_body<PHASE, true>(ps, num_wins, row_capacity);
+    else
+        plan_order_body<PHASE, false>(ps, num_wins, row_capacity);
 }
 
 // compact query rows: row q_off[w] + p = the p-th valid slot of window w's query list:
@@ -1135,12 +1211,16 @@ __global__ void __launch_bounds__(256) k_query_rows_vt(const int *num_wins, int 
 int mssvt_plan_order_multi_vt(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid, const int *host_nq,
                               const float *const *host_qmeta, int win_capacity, int row_capacity, int *const *host_perm,
                               int *const *host_num_active, int *const *host_q_off, float *const *host_qrow_meta,
-                              int *const *host_qrow_src, int *const *host_num_rows, const VtArgs *vt, void *stream) {
+                              int *const *host_qrow_src, int *const *host_num_rows, const VtArgs *vt, const PlanStepsArgs *sa,
+                              void *stream) {
+    if (sa && (sa->num_groups <= 0 || !sa->live || !sa->steps || !sa->num_steps || !sa->scratch)) return MSSVT_E_BADARG;
+    if (sa && num_sets > 0 && num_sets * (1 + sa->num_groups) > PO_MAX_ROWS) return MSSVT_E_TOOLARGE;
     if (num_sets <= 0 || num_sets > PO_MAX_SETS) return num_sets <= 0 ? MSSVT_E_BADARG : MSSVT_E_TOOLARGE;
     if (!num_wins_dev || !host_nq_valid || !host_nq || !host_qmeta || !host_perm || !host_num_active || !host_q_off ||
         !host_qrow_meta || !host_qrow_src || !host_num_rows || win_capacity <= 0 || row_capacity <= 0)
         return MSSVT_E_BADARG;
     PlanOrderPack pack;
+    for (int i = 0; i < PO_MAX_ROWS; ++i) pack.s[i].steps = nullptr;
     for (int i = 0; i < PO_MAX_SETS; ++i) {
         const int k = i < num_sets ? i : 0;
         if (!host_nq_valid[k] || !host_qmeta[k] || !host_perm[k] || !host_num_active[k] || !host_q_off[k] ||
@@ -1155,16 +1235,33 @@ int mssvt_plan_order_multi_vt(int num_sets, const int *num_wins_dev, const int *
         ps.num_rows = host_num_rows[k];
         ps.rmeta = reinterpret_cast<float4 *>(host_qrow_meta[k]);
         ps.rsrc = reinterpret_cast<int2 *>(host_qrow_src[k]);
+        ps.live = nullptr; ps.steps = nullptr; ps.num_steps = nullptr; ps.scratch = nullptr;
+    }
+    // step-list rows behind the query lists: row num_sets + i * num_groups + g = list i, head group g
+    int rows = num_sets;
+    if (sa) {
+        for (int i = 0; i < num_sets; ++i)
+            for (int g = 0; g < sa->num_groups; ++g) {
+                const int r = i * sa->num_groups + g;
+                if (!sa->live[g] || !sa->steps[r] || !sa->num_steps[r]) return MSSVT_E_BADARG;
+                PlanOrderSet &ps = pack.s[rows];
+                ps = pack.s[i];
+                ps.live = sa->live[g];
+                ps.steps = sa->steps[r];
+                ps.num_steps = sa->num_steps[r];
+                ps.scratch = sa->scratch + (size_t)(rows - num_sets) * PO_STEP_SCRATCH;
+                ++rows;
+            }
     }
     // workgroups per list: one per ~2k windows of capacity, as long as their histograms fit the head of the row array
     int G = win_capacity / 2048;
     if (G > 64) G = 64;
     while (G > 1 && (long long)G * (PO_KEYS + 1) > 2LL * row_capacity) --G;
     if (G > 1) {
-        k_plan_order<0><<<dim3(G, num_sets), PO_WAVES * MSSVT_WAVE, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
-        k_plan_order<1><<<dim3(G, num_sets), PO_WAVES * MSSVT_WAVE, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
+        k_plan_order<0><<<dim3(G, rows), PO_WAVES * MSSVT_WAVE, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
+        k_plan_order<1><<<dim3(G, rows), PO_WAVES * MSSVT_WAVE, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
     } else {
-        k_plan_order<1><<<dim3(1, num_sets), PO_WAVES * MSSVT_WAVE, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
+        k_plan_order<1><<<dim3(1, rows), PO_WAVES * MSSVT_WAVE, 0, (hipStream_t)stream>>>(num_wins_dev, row_capacity, pack);
     }
     int grid = (win_capacity + 3) / 4;
     if (grid > 4096) grid = 4096;
@@ -1182,7 +1279,26 @@ extern "C" int mssvt_plan_order_multi(int num_sets, const int *num_wins_dev, con
                                       int *const *host_q_off, float *const *host_qrow_meta,
                                       int *const *host_qrow_src, int *const *host_num_rows, void *stream) {
     return mssvt_plan_order_multi_vt(num_sets, num_wins_dev, host_nq_valid, host_nq, host_qmeta, win_capacity, row_capacity, host_perm,
-                                     host_num_active, host_q_off, host_qrow_meta, host_qrow_src, host_num_rows, nullptr, stream);
+                                     host_num_active, host_q_off, host_qrow_meta, host_qrow_src, host_num_rows, nullptr, nullptr, stream);
+}
+
+// mssvt_plan_order_multi that also emits, per (query list i, head group g), the step list of the paired window launch
+// (mssvt_block_attention_kv16_steps) in the same launches: host_steps[i * num_groups + g] (2 x win_capacity ints) and its
+// count, from the list's nq_valid and host_live[g], the plan kernel's flag of group g (mssvt_window_plan_two_live)
+extern "C" long long mssvt_plan_order_steps_scratch_ints(int num_sets, int num_groups) {
+    if (num_sets <= 0 || num_groups <= 0) return 0;
+    return (long long)num_sets * num_groups * PO_STEP_SCRATCH;
+}
+extern "C" int mssvt_plan_order_steps(int num_sets, const int *num_wins_dev, const int *const *host_nq_valid,
+                                      const int *host_nq, const float *const *host_qmeta, int win_capacity,
+                                      int row_capacity, int *const *host_perm, int *const *host_num_active,
+                                      int *const *host_q_off, float *const *host_qrow_meta,
+                                      int *const *host_qrow_src, int *const *host_num_rows, int num_groups,
+                                      const int *const *host_live, int *const *host_steps, int *const *host_num_steps,
+                                      int *scratch, void *stream) {
+    const PlanStepsArgs sa{num_groups, host_live, host_steps, host_num_steps, scratch};
+    return mssvt_plan_order_multi_vt(num_sets, num_wins_dev, host_nq_valid, host_nq, host_qmeta, win_capacity, row_capacity, host_perm,
+                                     host_num_active, host_q_off, host_qrow_meta, host_qrow_src, host_num_rows, nullptr, &sa, stream);
 }
 
 extern "C" int mssvt_plan_order(const int *num_wins_dev, const int *nq_valid, int nq, const float *qmeta,
