@@ -1085,6 +1085,49 @@ int mssvt_bev_conv_pack(const float *weight, int transposed, const float *bias, 
 int mssvt_bev_conv(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride,
                    int dilation, int relu, int *exp_workspace, float *y, void *stream);
 
+/* CenterHead's convolutions in eval mode as three launches (csrc/head_conv.hip; ref pcdet/models/dense_heads/center_head.py:
+ * shared_conv :76-84, SeparateHead :11-46, forward :350-360), in the arithmetic of mssvt_bev_conv (split-fp16 operands, three
+ * matrix instructions per product sum, fp32 scale / shift in the epilogue, exact power-of-two normalisation per output pixel
+ * and per weight tensor).  All tensors channels-last f32, 3x3, stride 1, zero padding 1.  Inference only.
+ *   shared: x (B, H, W, cin) -> (B, H, W, s) = relu(bn(conv)), cin in {64, 256, 384, 512}, s in {32, 64};
+ *   trunk:  the first Conv + BN + ReLU of all nb branches (of all heads) as one convolution s -> nb s: (B, H, W, nb s);
+ *   finals: the last convolution of every branch, s -> k_b <= 16 with bias and no activation; branch b reads channels
+ *           [b s, (b + 1) s) of the trunk tensor and writes PLANAR: its maps are the contiguous (B, k_b, H, W) block at float
+ *           offset kbase_b B H W of y, kbase_b = the maps of the branches before it (y holds B H W sum k_b floats).
+ * Exponent words: one int32 per (pixel, branch) = the largest |value| over the channels a later stage normalises together,
+ * as bits.  mssvt_head_conv_shared writes the input's into exp_workspace (B H W) itself and leaves its output's in exp_out
+ * (B H W); mssvt_head_conv_trunk reads those and leaves exp_out (B H W, nb), one word per pixel AND BRANCH, which
+ * mssvt_head_conv_finals reads: every branch is normalised on its own slice.  mssvt_head_conv_expmap computes the words of any
+ * (rows, c) matrix, c in {32, 64, 256, 384, 512} (a tensor that another producer wrote: rows = B H W, or B H W nb with c = s).
+ * mssvt_head_conv_supported: 1 if the three stages cover a head with these sizes (nb <= 64 branches, kmax = max k_b <= 16).
+ * Packed blobs: 16 bytes per slice {float 2^-e, float 2^e, int k, int kbase} padded to 64, scale then shift (slices x NS) f32,
+ * then per slice, tap and 128-channel chunk of the input the hi and the lo fp16 image as operand fragments (NS = s; 16 for
+ * the finals, rows beyond k_b zero).  *_pack_bytes: the size (0: not covered).  mssvt_head_conv_shared_pack packs the whole
+ * blob; mssvt_head_conv_trunk_pack / mssvt_head_conv_finals_pack pack ONE branch per call into the blob of nb branches
+ * (weight (s, s, 3, 3) / (k, s, 3, 3) as Conv2d holds it; BatchNorm2d in eval mode folded as in mssvt_bev_conv_pack; two
+ * launches each, no host read).  Never reads outside its inputs, writes every output element exactly once, bit-identical
+ * from call to call.  Null / unaligned (16 bytes: x, y, packed) pointers, sizes < 1, branch outside [0, nb): MSSVT_E_BADARG;
+ * sizes outside the sets above, k > 16, B H W >= 2^31 - 1024: MSSVT_E_TOOLARGE; neither launches anything.              */
+int mssvt_head_conv_supported(int cin, int s, int nb, int kmax);
+long long mssvt_head_conv_shared_pack_bytes(int cin, int s);
+long long mssvt_head_conv_trunk_pack_bytes(int s, int nb);
+long long mssvt_head_conv_finals_pack_bytes(int s, int nb);
+int mssvt_head_conv_shared_pack(const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                const float *bn_mean, const float *bn_var, float bn_eps, int cin, int s, void *packed,
+                                void *stream);
+int mssvt_head_conv_trunk_pack(const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                               const float *bn_mean, const float *bn_var, float bn_eps, int s, int nb, int branch,
+                               void *packed, void *stream);
+int mssvt_head_conv_finals_pack(const float *weight, const float *bias, int s, int nb, int branch, int k, int kbase,
+                                void *packed, void *stream);
+int mssvt_head_conv_expmap(const float *x, long long rows, int c, int *exp_words, void *stream);
+int mssvt_head_conv_shared(const float *x, int B, int H, int W, int cin, int s, const void *packed, int *exp_workspace,
+                           float *y, int *exp_out, void *stream);
+int mssvt_head_conv_trunk(const float *x, int B, int H, int W, int s, int nb, const void *packed, const int *exp_in,
+                          float *y, int *exp_out, void *stream);
+int mssvt_head_conv_finals(const float *x, int B, int H, int W, int s, int nb, const void *packed, const int *exp_in,
+                           float *y, void *stream);
+
 /* DynamicVFE's two PFN layers in eval mode as two launches (csrc/pfn_fused.hip; ref
  * pcdet/models/backbones_3d/vfe/dynamic_vfe.py:96-131, PFNLayerV2 :14-52), default configuration: 5 point features + cluster
  * offset + voxel-centre offset (11 inputs), NUM_FILTERS [64, 128].  points (P, stride >= 6) f32 rows [b, x, y, z, f4, f5];

@@ -9,14 +9,20 @@ class-agnostic rotated NMS of model_nms_utils.class_agnostic_nms (:6-38) on the 
 Training (``.train()``): ``assign_targets`` (:103-214: Gaussian heat maps with CornerNet's radius, sub-cell offsets, log sizes,
 cos / sin headings, flat cell indices, masks) and ``get_loss`` (:220-250: CenterNet focal loss on the clamped sigmoid + masked
 L1 on the gathered regression maps, ``code_weights`` / ``loc_weight``) -- pinned to a training step of the reference's own
-module with its own loss classes (tests/golden/det_head_train.npz: targets, loss terms, every parameter gradient)."""
+module with its own loss classes (tests/golden/det_head_train.npz: targets, loss terms, every parameter gradient).
+
+``fused_convs`` (off by default; yaml key ``FUSED_CONVS``): in eval mode with autograd off, an fp32 GPU input and no AMP, the
+convolutions of a head that ``head_conv.supported`` covers (every branch ``num_conv == 2`` with at most 16 maps, Cin in {64, 256,
+384, 512}, SHARED_CONV_CHANNEL in {32, 64}, BatchNorm2d with running statistics) run on csrc/head_conv.hip -- the stages that
+``head_conv.ROUTED`` names -- and produce the same ``pred_dicts``; decoding is unchanged.  Under any other condition, and for
+any other head, the forward is the library's, untouched."""
 import copy
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, iou3d_nms_utils
+from . import _lib, head_conv, iou3d_nms_utils
 
 
 def _get(cfg, key, default=None):
@@ -370,6 +376,9 @@ class CenterHead(nn.Module):
         self.padded_predictions = False  # eval forward: final_box_padded (no host sync) instead of final_box_dicts
         self.fused_loss = False  # get_loss on the GPU: center_loss per head, tb_dict as device tensors (no host sync)
         self._code_weights_dev = {}  # device -> LOSS_WEIGHTS.code_weights as a float32 tensor (get_loss with fused_loss)
+        # eval forward without autograd, fp32 on the GPU, no AMP (bev_conv.switch_applies) and a head head_conv.supported
+        # covers: the convolutions on csrc/head_conv.hip (the stages head_conv.ROUTED names); anything else: the library
+        self.fused_convs = bool(_get(model_cfg, "FUSED_CONVS", False))
 
     def label_tables(self):
         """int array [label 0..C][head]: the class inside the head that a box of that label gets, or -1 when the head
@@ -623,8 +632,11 @@ class CenterHead(nn.Module):
         return loss, tb
 
     def forward(self, data_dict):
-        x = self.shared_conv(data_dict["spatial_features_2d"])
-        pred_dicts = [head(x) for head in self.heads_list]
+        if self.fused_convs and head_conv.applies(self, data_dict["spatial_features_2d"]):
+            pred_dicts = head_conv.forward(self, data_dict["spatial_features_2d"])
+        else:
+            x = self.shared_conv(data_dict["spatial_features_2d"])
+            pred_dicts = [head(x) for head in self.heads_list]
         if self.training:
             self.forward_ret_dict["target_dicts"] = self.assign_targets(
                 data_dict["gt_boxes"], feature_map_size=data_dict["spatial_features_2d"].shape[2:])

@@ -121,6 +121,29 @@ def main(out_path):
             xr = torch.randn(2, 23, 29, cin, generator=g).clamp_(min=0).to(DEV).permute(0, 3, 1, 2)
             out["bev_conv_%d_%d_s%d_d%d" % (cin, cout, stride, dil)] = \
                 bev_conv.conv_bn_act(xr, bev_conv.pack(conv.to(DEV), None), True).cpu().numpy()
+    # --- csrc/head_conv.hip: shared layer, trunk and finals at the golden (64 -> 32) and the product (512 -> 64) channel counts:
+    # one and four input chunks, one to four column tiles, the planar 16-column tile
+    from mssvt_amd import head_conv
+    g = torch.Generator().manual_seed(13)
+
+    def conv3(cin, cout, bias):
+        conv = torch.nn.Conv2d(cin, cout, 3, padding=1, bias=bias)
+        with torch.no_grad():
+            conv.weight.copy_(torch.randn(conv.weight.shape, generator=g) * 0.1)
+            if bias:
+                conv.bias.copy_(torch.randn(cout, generator=g))
+        return conv.to(DEV)
+
+    for cin, s in ((64, 32), (512, 64)):
+        ks = (2, 1, 3, 2, 3)
+        with torch.no_grad():
+            xr = torch.randn(2, 23, 29, cin, generator=g).clamp_(min=0).to(DEV)
+            y, e = head_conv.run_shared(head_conv.pack_shared(conv3(cin, s, False), None), xr)
+            t, e2 = head_conv.run_trunk(head_conv.pack_trunk([(conv3(s, s, False), None) for _ in ks]), y, e)
+            maps = head_conv.run_finals(head_conv.pack_finals([conv3(s, k, True) for k in ks]), t, e2)
+        out["head_conv_shared_%d_%d" % (cin, s)] = y.cpu().numpy()
+        out["head_conv_trunk_%d_%d" % (s, len(ks))] = t.cpu().numpy()
+        out["head_conv_finals_%d" % s] = torch.cat([m.reshape(-1) for m in maps]).cpu().numpy()
     np.savez(out_path, **out)
     print("schedule probe: %d arrays from %s -> %s" % (len(out) - 1, _lib.LIB_PATH, out_path))
 
