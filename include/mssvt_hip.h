@@ -1054,7 +1054,8 @@ int mssvt_linear_rows_h(int M, int K, int N, const float *X, int ldx, const floa
                         int relu, float out_scale, float *Y, int ldy, void *stream);
 
 /* y = act(scale[c] * conv(x, w) + shift[c]) on channels-last fp32 tensors with split-fp16 matrix operands
- * (csrc/bev_conv.hip): the Conv2d + BatchNorm2d + ReLU triples of HeightCompression's compress_layers (ref
+ * (csrc/bev_conv.hip; the kernel is csrc/split_conv.hip.h's, shared with mssvt_head_conv_*): the Conv2d + BatchNorm2d +
+ * ReLU triples of HeightCompression's compress_layers (ref
  * pcdet/models/backbones_2d/map_to_bev/height_compression.py:20-39, applied to the grid of :41-45) and of BaseBEVBackbone's
  * blocks / 1x1 deblocks (ref pcdet/models/backbones_2d/base_bev_backbone.py:30-78, forward :87-112) in eval mode.
  * Inference only.  Tap sets: 3x3 with stride 1 or 2, dilation 1 or 2 and zero padding = dilation (ZeroPad2d(1) + padding 0
@@ -1086,7 +1087,7 @@ int mssvt_bev_conv(const float *x, int B, int H, int W, int cin, const void *pac
                    int dilation, int relu, int *exp_workspace, float *y, void *stream);
 
 /* CenterHead's convolutions in eval mode as three launches (csrc/head_conv.hip; ref pcdet/models/dense_heads/center_head.py:
- * shared_conv :76-84, SeparateHead :11-46, forward :350-360), in the arithmetic of mssvt_bev_conv (split-fp16 operands, three
+ * shared_conv :76-84, SeparateHead :11-46, forward :350-360), on the kernel of mssvt_bev_conv (csrc/split_conv.hip.h: split-fp16 operands, three
  * matrix instructions per product sum, fp32 scale / shift in the epilogue, exact power-of-two normalisation per output pixel
  * and per weight tensor).  All tensors channels-last f32, 3x3, stride 1, zero padding 1.  Inference only.
  *   shared: x (B, H, W, cin) -> (B, H, W, s) = relu(bn(conv)), cin in {64, 256, 384, 512}, s in {32, 64};

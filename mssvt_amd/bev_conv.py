@@ -94,19 +94,29 @@ _cache = weakref.WeakKeyDictionary()  # conv module -> (key, Packed)
 
 
 def _tensors(conv, bn):
-    ts = [conv.weight, conv.bias]
-    if bn is not None:
-        ts += [bn.weight, bn.bias, bn.running_mean, bn.running_var]
-    return ts
+    return [conv.weight, conv.bias] + ([None] * 4 if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var])
+
+
+def params(conv, bn, who="bev_conv.pack"):
+    """[weight, bias, bn weight, bn bias, running mean, running var] of (conv, bn), checked fp32 on one GPU, detached and
+    contiguous (None where the layer has none)."""
+    ts = _tensors(conv, bn)
+    for t in ts:
+        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.device == conv.weight.device):
+            raise MssvtHipError("%s: parameters must be fp32 tensors on one GPU (no CPU path)" % who)
+    return [None if t is None else t.detach().contiguous() for t in ts]
+
+
+def pair_key(conv, bn):
+    """The cache-key element of (conv, bn): the modules' identity and every tensor's identity, storage and version
+    (load_state_dict and an optimizer step write in place: version; .to() and a re-assigned parameter change the identity
+    or the storage)."""
+    return (id(conv), id(bn), None if bn is None else float(bn.eps)) + tuple(
+        None if t is None else (id(t), t.data_ptr(), t._version, str(t.device)) for t in _tensors(conv, bn))
 
 
 def _key(conv, bn, pad):
-    # tensor identity, storage and version: load_state_dict and an optimizer step write in place (version), .to() and a
-    # re-assigned parameter change the identity or the storage
-    k = [id(bn), None if bn is None else float(bn.eps), pad]
-    for t in _tensors(conv, bn):
-        k.append(None if t is None else (id(t), t.data_ptr(), t._version, str(t.device)))
-    return tuple(k)
+    return (pair_key(conv, bn), pad)
 
 
 @torch.no_grad()
@@ -121,11 +131,7 @@ def pack(conv, bn=None, pad=None):
         raise MssvtHipError("bev_conv.pack: layer not covered (%r, %r)" % (conv, bn))
     shape = layer_shape(conv, pad)
     ksize, cin, cout = shape[:3]
-    ts = _tensors(conv, bn) + ([None] * 4 if bn is None else [])
-    for t in ts:
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.device == conv.weight.device):
-            raise MssvtHipError("bev_conv.pack: parameters must be fp32 tensors on one GPU")
-    w, bias, bn_w, bn_b, bn_m, bn_v = [None if t is None else t.detach().contiguous() for t in ts]
+    w, bias, bn_w, bn_b, bn_m, bn_v = params(conv, bn)
     nbytes = _lib.lib().mssvt_bev_conv_pack_bytes(ksize, cin, cout)
     blob = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
     with torch.cuda.device(w.device):

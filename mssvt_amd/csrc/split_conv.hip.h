@@ -1,0 +1,362 @@
+// split_conv.hip.h -- y = act(scale[c] * conv(x, w) + shift[c]) on channels-last fp32 pixels with split-fp16 matrix operands:
+// the one kernel (k_split_conv), exponent-word kernel and weight packer behind bev_conv.hip and head_conv.hip.
+// The library runs these convolutions on the fp32 matrix instruction (1/16 of the 16-bit rate); here every fp32 operand v is
+// carried as hi = fp16(v), lo = fp16((v - hi) 2^11), a product sum = hi hi + 2^-11 (hi lo + lo hi) on v_mfma_f32_16x16x32_f16
+// with fp32 accumulation: the arithmetic of k_linear_rows_h (csrc/linear_rows_h.hip), with both halves rounded to NEAREST here
+// (each operand is then off by at most 2^-23 of itself and the dropped lo lo term is at most 2^-22 of the product).
+//
+// A convolution over channels-last pixels is one row-GEMM per tap accumulated into one tile: M = output pixels, N = output
+// columns, K = taps x Cin.  Nothing per tap is ever written to global memory: the lanes of a wave read the tap's input pixel
+// of THEIR output pixel straight from x (32 bytes per lane and k step; a pixel outside the image is produced as zeros, never
+// loaded).
+//
+//   * a wave owns BC_WAVE_PIXELS = 32 consecutive output pixels (two 16-row operand tiles that share every weight fragment
+//     read) and NS <= 128 output columns; all 2 x NS / 16 accumulator tiles (mm: hi hi, cr: the cross terms) stay in
+//     registers over every tap and all of Cin -- one accumulation chain per output element;
+//   * a workgroup is 8 waves = BC_BLOCK_PIXELS = 256 output pixels; blockIdx.y is a SLICE of NS output columns;
+//   * the weights arrive packed (k_split_pack): per (slice, tap, 128-channel chunk of Cin) one contiguous block holding the hi
+//     and the lo image as ready operand fragments [k step][column tile][lane] x 16 bytes.  A block (<= 64 KiB) is copied into
+//     one of two LDS buffers while the previous one is multiplied: one barrier per block;
+//   * range: fp16 is narrow, so every OUTPUT pixel's operands are normalised by one exact power of two taken from the largest
+//     exponent over its whole receptive field (k_split_expmap, or a previous launch's epilogue, leaves one word per input
+//     pixel), and the weights by one power of two per header record (at pack time); both are undone in the epilogue, exactly.
+//     Scaling the input by a power of two therefore scales the result bit for bit;
+//   * the epilogue applies scale / shift in fp32 (the BatchNorm fold is NOT rounded into the fp16 weights), the activation,
+//     and stores; every output element has exactly one writer, no atomics.
+//
+// blob: [nsl records of 16 bytes: float w_in (2^-e), float w_un (2^e), int k (columns in use), int kbase (maps before it);
+// zero-padded to 64 bytes][scale nsl NS][shift nsl NS][per slice: its weight blocks].
+#pragma once
+#include "common.hip.h"
+
+typedef float bc_f32x4 __attribute__((ext_vector_type(4)));
+typedef float bc_f32x2 __attribute__((ext_vector_type(2)));
+typedef _Float16 bc_h16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 bc_h16x2 __attribute__((ext_vector_type(2)));
+
+#define BC_WAVES 8
+#define BC_WAVE_PIXELS MSSVT_BEV_CONV_WAVE_PIXELS
+#define BC_BLOCK_PIXELS MSSVT_BEV_CONV_BLOCK_PIXELS
+#define BC_THREADS (BC_WAVES * MSSVT_WAVE)
+#define BC_SCALE 2048.0f
+#define BC_INV (1.0f / 2048.0f)
+#define BC_REC_BYTES 16
+#define BC_HDR(NSL) ((((NSL) * BC_REC_BYTES) + 63) / 64 * 64)
+#define BC_MFMA(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
+static_assert(BC_WAVE_PIXELS == 32 && BC_BLOCK_PIXELS == BC_WAVES * BC_WAVE_PIXELS, "tile constants of the header");
+
+#define BC_KC(CIN) ((CIN) < 128 ? (CIN) : 128)  // input channels per staged weight block
+
+// 8 floats (scaled by the exact power of two s) -> hi and lo halves, both rounded to nearest even
+__device__ __forceinline__ void bc_split8(const float4 v0, const float4 v1, float s, bc_h16x8 &hi, bc_h16x8 &lo) {
+    const float x[8] = {v0.x * s, v0.y * s, v0.z * s, v0.w * s, v1.x * s, v1.y * s, v1.z * s, v1.w * s};
+#pragma unroll
+    for (int i = 0; i < 8; i += 2) {
+        const bc_h16x2 a = __builtin_convertvector((bc_f32x2{x[i], x[i + 1]}), bc_h16x2);
+        // x 2^11 - hi 2^11: exact (the residual of a 24-bit value against its 11-bit rounding has at most 13 bits)
+        const bc_f32x2 r = {__builtin_fmaf((float)a[0], -BC_SCALE, x[i] * BC_SCALE),
+                            __builtin_fmaf((float)a[1], -BC_SCALE, x[i + 1] * BC_SCALE)};
+        const bc_h16x2 c = __builtin_convertvector(r, bc_h16x2);
+        hi[i] = a[0]; hi[i + 1] = a[1];
+        lo[i] = c[0]; lo[i + 1] = c[1];
+    }
+}
+
+// |v| as an integer: ordered like the magnitudes, every NaN above infinity (fmaxf would drop a NaN)
+__device__ __forceinline__ int bc_abs_bits(float v) { return __builtin_bit_cast(int, v) & 0x7FFFFFFF; }
+
+static bool bc_misaligned(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15) != 0; }
+static bool bc_too_many_pixels(int B, int H, int W) { return (long long)B * H * W > 0x7FFFFFFFll - 4 * BC_BLOCK_PIXELS; }
+
+// ---- one word per row of a (rows, C) matrix: the largest |x| of the row, as bits; LPR lanes share a row ------------------
+template <int C, int LPR>
+__global__ void __launch_bounds__(256) k_split_expmap(const float *x, long long rows, int *emap) {
+    constexpr int RPW = MSSVT_WAVE / LPR;  // rows per wave
+    const int lane = lane_id(), sub = lane % LPR;
+    const long long row = ((long long)blockIdx.x * 4 + threadIdx.x / MSSVT_WAVE) * RPW + lane / LPR;
+    int m = 0;
+    if (row < rows) {
+#pragma unroll
+        for (int c = 0; c < C / 4; c += LPR) {
+            const float4 v = *reinterpret_cast<const float4 *>(x + (size_t)row * C + 4 * (c + sub));
+            m = max(m, max(max(bc_abs_bits(v.x), bc_abs_bits(v.y)), max(bc_abs_bits(v.z), bc_abs_bits(v.w))));
+        }
+    }
+#pragma unroll
+    for (int off = LPR / 2; off >= 1; off >>= 1) m = max(m, __shfl_xor(m, off));
+    if (row < rows && sub == 0) emap[row] = m;
+}
+
+template <int C, int LPR>
+static int bc_expmap(const float *x, long long rows, int *emap, hipStream_t st) {
+    k_split_expmap<C, LPR><<<divup(rows, 4 * (MSSVT_WAVE / LPR)), 256, 0, st>>>(x, rows, emap);
+    return mssvt_launch_status();
+}
+
+// ---- the convolution ---------------------------------------------------------------------------------------------------
+template <int CIN, int NS>
+struct bc_geom {
+    static constexpr int KC = BC_KC(CIN), KS = KC / 32, NT = NS / 16, CHUNKS = CIN / KC;
+    static constexpr int IMG = KS * NT * 64;  // 16-byte fragments per (hi or lo) image of a block
+    static constexpr size_t LDS = 2 * (size_t)2 * IMG * 16;  // two buffers of a hi and a lo image
+};
+
+enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR };  // OUT: y (M, nsl NS) rows; rows and eout [pixel][nsl], the largest |y| of the
+                                             // pixel's slice as bits; slice sl's k <= 16 maps planar at float kbase B H W
+
+// TAPS 0: ksize x ksize taps (3: padding = dil, 1: none) at `stride` / `dil`, output Ho x Wo;  TAPS 3: 3 x 3, stride 1,
+// dilation 1, Ho = H, Wo = W as constants (those five arguments are not read).
+// SLICED false: pixels of CIN floats, one exponent word per pixel, every slice under header record 0;  true: pixels of
+// `xstride` floats of which slice sl reads channels [sl gin, sl gin + CIN), emap [pixel][egroups] of which it reads word sl
+// when egroups > 1 (else word 0), and header record sl.
+template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
+__global__ void __launch_bounds__(BC_THREADS, 1)
+    k_split_conv(const float *x, int xstride_, int gin, int H, int W, int Ho_, int Wo_, int M, const unsigned char *blob, int nsl,
+                 int ksize_, int stride_, int dil_, const int *emap, int egroups_, int relu, float *y, int *eout) {
+    using G = bc_geom<CIN, NS>;
+    constexpr int KC = G::KC, KS = G::KS, NT = G::NT, CHUNKS = G::CHUNKS, IMG = G::IMG;
+    constexpr int FR = (2 * IMG + BC_THREADS - 1) / BC_THREADS;  // fragments of a block per thread ...
+    constexpr int FP = (FR + KS - 1) / KS;  // ... of which a thread moves at most FP under each k step of the previous block
+    extern __shared__ float4 bc_lds[];
+    bc_h16x8 *lds = reinterpret_cast<bc_h16x8 *>(bc_lds);  // two buffers of 2 IMG fragments
+    const int lane = lane_id(), la = lane & 15, g = lane >> 4;
+    const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / MSSVT_WAVE);
+    const int ksize = TAPS ? TAPS : ksize_, stride = TAPS ? 1 : stride_, dil = TAPS ? 1 : dil_;
+    const int Ho = TAPS ? H : Ho_, Wo = TAPS ? W : Wo_, HWo = Ho * Wo;
+    const int nstages = ksize * ksize * CHUNKS, pad = ksize == 3 ? dil : 0;
+    const int sl = blockIdx.y, cout = nsl * NS, hdr = SLICED ? BC_HDR(nsl) : BC_HDR(1);
+    const int xstride = SLICED ? xstride_ : CIN, cbase = SLICED ? sl * gin : 0;
+    const int egroups = SLICED ? egroups_ : 1, eoff = egroups > 1 ? sl : 0;
+    const float *rec = reinterpret_cast<const float *>(blob + (SLICED ? (size_t)sl * BC_REC_BYTES : 0));
+    const float w_un = rec[1];
+    const float *scale = reinterpret_cast<const float *>(blob + hdr) + sl * NS, *shift = scale + cout;
+    const bc_h16x8 *wsrc = reinterpret_cast<const bc_h16x8 *>(blob + hdr + (size_t)cout * 8) + (size_t)sl * nstages * 2 * IMG;
+    // block 0 of the weights -> LDS buffer 0
+#pragma unroll
+    for (int i = 0; i < FR; ++i) {
+        const int f = threadIdx.x + i * BC_THREADS;
+        if (f < 2 * IMG) lds[f] = wsrc[f];
+    }
+    // the wave's two 16-pixel tiles: lane (la, g) reads channels 8 g .. of pixel la of each tile
+    int oy0[2], ox0[2];
+    int img[2];  // first pixel of the tile's sample (B H W < 2^31)
+    bool live[2];
+    float s_in[2], un[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int m = blockIdx.x * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la;
+        live[j] = m < M;
+        const int mc = live[j] ? m : 0, b = mc / HWo, r = mc - b * HWo, oy = r / Wo;
+        oy0[j] = oy * stride - pad;
+        ox0[j] = (r - oy * Wo) * stride - pad;
+        img[j] = b * (H * W);
+        // the pixel's power of two: the largest exponent over its receptive field (all taps inside the image)
+        int e = 0;
+        if (live[j])
+            for (int ky = 0; ky < ksize; ++ky)
+                for (int kx = 0; kx < ksize; ++kx) {
+                    const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
+                    if (iy >= 0 && iy < H && ix >= 0 && ix < W) e = max(e, emap[(size_t)(img[j] + iy * W + ix) * egroups + eoff]);
+                }
+        const int eb = e & 0x7F800000;
+        const bool norm = eb != 0 && eb < 0x7F000000;  // zero / denormal fields and inf / nan fields pass through unscaled
+        s_in[j] = norm ? __builtin_bit_cast(float, 0x7F000000 - eb) : 1.0f;
+        un[j] = (norm ? __builtin_bit_cast(float, eb) : 1.0f) * w_un;
+    }
+    bc_f32x4 mm[2][NT], cr[2][NT];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) mm[j][t] = cr[j][t] = bc_f32x4{0.f, 0.f, 0.f, 0.f};
+    // the operand rows of k step (stage, P): 8 floats per tile, zeros where the tap falls outside the image
+    float4 xa[2][2];
+    auto load_rows = [&](int st, int P) {
+        const int tap = st / CHUNKS, chunk = st - tap * CHUNKS;
+        const int ky = (tap >= ksize) + (tap >= 2 * ksize), kx = tap - ky * ksize;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
+            xa[j][0] = xa[j][1] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (live[j] && iy >= 0 && iy < H && ix >= 0 && ix < W) {
+                const float *p = x + (size_t)(img[j] + iy * W + ix) * xstride + cbase + chunk * KC + 32 * P + 8 * g;
+                xa[j][0] = *reinterpret_cast<const float4 *>(p);
+                xa[j][1] = *reinterpret_cast<const float4 *>(p + 4);
+            }
+        }
+    };
+    load_rows(0, 0);
+    __syncthreads();
+    for (int st = 0; st < nstages; ++st) {
+        const bool more = st + 1 < nstages;
+        const bc_h16x8 *Bh = lds + (st & 1) * 2 * IMG, *Bl = Bh + IMG;
+        bc_h16x8 *dst = lds + ((st + 1) & 1) * 2 * IMG;  // last read during block st - 1: behind the previous barrier
+#pragma unroll
+        for (int P = 0; P < KS; ++P) {
+            bc_h16x8 wreg[FP];
+            if (more) {  // a piece of the next block's fragments travels under this k step's products
+#pragma unroll
+                for (int i = 0; i < FP; ++i) {
+                    const int f = threadIdx.x + (P * FP + i) * BC_THREADS;
+                    if (P * FP + i < FR && f < 2 * IMG) wreg[i] = wsrc[(size_t)(st + 1) * 2 * IMG + f];
+                }
+            }
+            bc_h16x8 ah[2], al[2];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) bc_split8(xa[j][0], xa[j][1], s_in[j], ah[j], al[j]);
+            if (P + 1 < KS) load_rows(st, P + 1);
+            else if (more) load_rows(st + 1, 0);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                const bc_h16x8 bh = Bh[(P * NT + t) * 64 + lane], bl = Bl[(P * NT + t) * 64 + lane];
+                // Y^T tile: A = the weights' rows n, B = the tile's pixels m
+                BC_MFMA(mm[0][t], bh, ah[0]);
+                BC_MFMA(mm[1][t], bh, ah[1]);
+                BC_MFMA(cr[0][t], bh, al[0]);
+                BC_MFMA(cr[1][t], bh, al[1]);
+                BC_MFMA(cr[0][t], bl, ah[0]);
+                BC_MFMA(cr[1][t], bl, ah[1]);
+            }
+            if (more) {
+#pragma unroll
+                for (int i = 0; i < FP; ++i) {
+                    const int f = threadIdx.x + (P * FP + i) * BC_THREADS;
+                    if (P * FP + i < FR && f < 2 * IMG) dst[f] = wreg[i];
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);  // (keeps the fragment reads of later k steps from being hoisted: spills)
+        }
+        __syncthreads();
+    }
+    // epilogue: lane (m = la, g) holds y[m][16 t + 4 g + i] of its slice
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (OUT != BC_ROWS_WORDS && !live[j]) continue;  // (with words the whole wave takes part in the exchange below)
+        const int m = blockIdx.x * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la, mc = live[j] ? m : 0;
+        int top = 0;  // the largest |y| of the lane's columns, as bits
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float4 s4 = *reinterpret_cast<const float4 *>(scale + 16 * t + 4 * g);
+            const float4 b4 = *reinterpret_cast<const float4 *>(shift + 16 * t + 4 * g);
+            const float sv[4] = {s4.x, s4.y, s4.z, s4.w}, bv[4] = {b4.x, b4.y, b4.z, b4.w};
+            float o[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                // (x s_in) (w w_in) / (s_in w_in): both normalisations undone by exact powers of two, then scale / shift
+                const float r = __builtin_fmaf(cr[j][t][i], BC_INV, mm[j][t][i]) * un[j];
+                o[i] = __builtin_fmaf(r, sv[i], bv[i]);
+                if (relu) o[i] = o[i] < 0.f ? 0.f : o[i];  // (a NaN stays a NaN: fmaxf would turn it into 0)
+                top = max(top, bc_abs_bits(o[i]));
+            }
+            if (!live[j]) continue;
+            if (OUT == BC_PLANAR) {  // the address is formed per pixel: a wave's tile may straddle two samples
+                const int kcols = reinterpret_cast<const int *>(rec)[2], kbase = reinterpret_cast<const int *>(rec)[3];
+                const int b = mc / HWo, r = mc - b * HWo;
+                float *out = y + ((size_t)kbase * (M / HWo) + (size_t)b * kcols) * HWo + r;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+                    if (4 * g + i < kcols) out[(size_t)(4 * g + i) * HWo] = o[i];
+            } else {
+                *reinterpret_cast<float4 *>(y + (size_t)mc * cout + sl * NS + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
+            }
+        }
+        if (OUT == BC_ROWS_WORDS) {
+            top = max(top, __shfl_xor(top, 16));
+            top = max(top, __shfl_xor(top, 32));
+            if (live[j] && g == 0) eout[(size_t)mc * nsl + sl] = top;
+        }
+    }
+}
+
+template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
+static int bc_launch(const float *x, int xstride, int gin, int H, int W, int Ho, int Wo, int M, const void *packed, int nsl,
+                     int ksize, int stride, int dil, const int *emap, int egroups, int relu, float *y, int *eout, hipStream_t st) {
+    const auto kernel = k_split_conv<CIN, NS, TAPS, SLICED, OUT>;
+    constexpr size_t LDS = bc_geom<CIN, NS>::LDS;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
+    if (e != hipSuccess) return (int)e;
+    kernel<<<dim3(divup(M, BC_BLOCK_PIXELS), nsl), BC_THREADS, LDS, st>>>(
+        x, xstride, gin, H, W, Ho, Wo, M, reinterpret_cast<const unsigned char *>(packed), nsl, ksize, stride, dil, emap, egroups,
+        relu, y, eout);
+    return mssvt_launch_status();
+}
+
+// ---- weight packing: the slices [sl, sl + n) of a blob of nsl from one weight tensor of k <= n ns output channels ---------
+// (n = nsl, sl = 0 if `whole`, else n = 1).  The kernels are static: both translation units hold a copy.
+// one workgroup: the power of two of the tensor's weights and the n ns folded scale / shift columns.  whole: record 0 and
+// its zero padding to 64 bytes, [w_in, w_un, 0 ..]; else record sl, [w_in, w_un, k, kbase]
+static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long long count, const float *bias, const float *bn_w,
+                                                            const float *bn_b, const float *bn_mean, const float *bn_var,
+                                                            float eps, int k, int kbase, int ns, int nsl, int sl, int whole,
+                                                            unsigned char *blob) {
+    __shared__ int part[16];
+    int m = 0;
+    for (long long i = threadIdx.x; i < count; i += blockDim.x) m = max(m, bc_abs_bits(w[i]));
+    for (int off = 32; off; off >>= 1) m = max(m, __shfl_xor(m, off));
+    if (lane_id() == 0) part[threadIdx.x / MSSVT_WAVE] = m;
+    __syncthreads();
+    if (threadIdx.x < (whole ? 16 : 4)) {
+        m = 0;
+        for (int i = 0; i < 16; ++i) m = max(m, part[i]);
+        const int eb = m & 0x7F800000;
+        const bool norm = eb != 0 && eb < 0x7F000000;
+        const int word[4] = {norm ? 0x7F000000 - eb : 0x3F800000, norm ? eb : 0x3F800000, whole ? 0 : k, whole ? 0 : kbase};
+        reinterpret_cast<int *>(blob + (size_t)sl * BC_REC_BYTES)[threadIdx.x] = threadIdx.x < 4 ? word[threadIdx.x] : 0;
+    }
+    const int cols = (whole ? nsl : 1) * ns;
+    float *scale = reinterpret_cast<float *>(blob + BC_HDR(nsl)) + (size_t)sl * ns, *shift = scale + (size_t)nsl * ns;
+    for (int c = threadIdx.x; c < cols; c += blockDim.x) {
+        // BatchNorm2d in eval mode: y = (v + bias - mean) gamma / sqrt(var + eps) + beta, folded in double, rounded once;
+        // a column beyond k (the 16-column tile of a narrower branch) is never stored: scale 1, shift 0
+        double s = 1.0, t = (bias && c < k) ? (double)bias[c] : 0.0;
+        if (bn_mean && c < k) {
+            s = (bn_w ? (double)bn_w[c] : 1.0) / sqrt((double)bn_var[c] + (double)eps);
+            t = (t - (double)bn_mean[c]) * s + (bn_b ? (double)bn_b[c] : 0.0);
+        }
+        scale[c] = (float)s;
+        shift[c] = (float)t;
+    }
+}
+
+// one thread per operand fragment: (slice, stage = (tap, chunk), P, t, lane) -> 8 weights of output channel n = slice ns +
+// 16 t + lane % 16 of the tensor (zeros beyond k), c = chunk KC + 32 P + 8 (lane / 16) .., split into the hi and the lo image
+// of the stage's block.  The tensor is a Conv2d weight (k, cin, ksize, ksize), or (cin, k, 1, 1) if `transposed`
+static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int transposed, int ksize, int cin, int k, int ns,
+                                                           int nsl, int sl, int n_slices, unsigned char *blob) {
+    const int KC = BC_KC(cin), KS = KC / 32, NT = ns / 16, CHUNKS = cin / KC, IMG = KS * NT * 64;
+    const int ntaps = ksize * ksize, nstages = ntaps * CHUNKS;
+    const long long total = (long long)n_slices * nstages * IMG, id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (id >= total) return;
+    const int f = (int)(id % IMG), st = (int)((id / IMG) % nstages), slice = (int)(id / ((long long)IMG * nstages));
+    const int ln = f & 63, t = (f >> 6) % NT, P = (f >> 6) / NT;
+    const int tap = st / CHUNKS, chunk = st - tap * CHUNKS;
+    const int n = slice * ns + 16 * t + (ln & 15), c0 = chunk * KC + 32 * P + 8 * (ln >> 4);
+    const float w_in = reinterpret_cast<const float *>(blob + (size_t)sl * BC_REC_BYTES)[0];
+    float v[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i)
+        v[i] = n >= k ? 0.f : transposed ? w[(size_t)(c0 + i) * k + n] : w[((size_t)n * cin + c0 + i) * ntaps + tap];
+    bc_h16x8 h, l;
+    bc_split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), w_in, h, l);
+    bc_h16x8 *blk = reinterpret_cast<bc_h16x8 *>(blob + BC_HDR(nsl) + (size_t)nsl * ns * 8) +
+                    ((size_t)(sl + slice) * nstages + st) * 2 * IMG;
+    blk[f] = h;
+    blk[IMG + f] = l;
+}
+
+static bool bc_bad_bn(const float *bn_w, const float *bn_b, const float *bn_mean, const float *bn_var, float eps) {
+    return (!bn_mean != !bn_var) || ((bn_w || bn_b) && !bn_mean) || (bn_mean && !(eps >= 0.f));
+}
+
+static int bc_pack(const float *w, int transposed, const float *bias, const float *bn_w, const float *bn_b, const float *bn_mean,
+                   const float *bn_var, float eps, int ksize, int cin, int k, int kbase, int ns, int nsl, int sl, int whole,
+                   void *packed, hipStream_t st) {
+    unsigned char *blob = reinterpret_cast<unsigned char *>(packed);
+    const int n_slices = whole ? nsl : 1;
+    k_split_prep<<<1, 1024, 0, st>>>(w, (long long)ksize * ksize * cin * k, bias, bn_w, bn_b, bn_mean, bn_var, eps, k, kbase, ns,
+                                     nsl, sl, whole, blob);
+    int status = mssvt_launch_status();
+    if (status != MSSVT_OK) return status;
+    k_split_pack<<<divup((long long)n_slices * ksize * ksize * cin * ns / 8, 256), 256, 0, st>>>(w, transposed, ksize, cin, k, ns,
+                                                                                                 nsl, sl, n_slices, blob);
+    return mssvt_launch_status();
+}

@@ -27,7 +27,7 @@ from torch import nn
 
 from . import _lib
 from ._lib import MssvtHipError
-from .bev_conv import is_channels_last, switch_applies
+from .bev_conv import is_channels_last, pair_key, params, switch_applies
 
 STAGES = ("shared", "trunk", "finals")
 # the stages that cleared the routing rule on an MI355X at the mssvt.yaml head shape (profiles/head_conv_times.json: all
@@ -113,12 +113,7 @@ class Packed(object):
 
 
 def _params(conv, bn):
-    ts = [conv.weight, conv.bias] + ([None] * 4 if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var])
-    dev = conv.weight.device
-    for t in ts:
-        if t is not None and not (t.is_cuda and t.dtype == torch.float32 and t.device == dev):
-            raise MssvtHipError("head_conv: parameters must be fp32 tensors on one GPU (no CPU path)")
-    return [None if t is None else t.detach().contiguous() for t in ts]
+    return params(conv, bn, "head_conv")
 
 
 def _blob(nbytes, device):
@@ -175,15 +170,8 @@ _cache = weakref.WeakKeyDictionary()  # CenterHead -> (key, {stage: Packed})
 
 
 def _key(found):
-    # bev_conv._key's rule over all of the head's tensors: identity, storage and version (load_state_dict and an optimizer
-    # step write in place; .to() and a re-assigned parameter change the identity or the storage)
     shared, trunk, finals = found
-    k = []
-    for conv, bn in [shared] + list(trunk) + [(c, None) for c in finals]:
-        k.append((id(conv), id(bn), None if bn is None else float(bn.eps)))
-        for t in [conv.weight, conv.bias] + ([] if bn is None else [bn.weight, bn.bias, bn.running_mean, bn.running_var]):
-            k.append(None if t is None else (id(t), t.data_ptr(), t._version, str(t.device)))
-    return tuple(k)
+    return tuple(pair_key(conv, bn) for conv, bn in [shared] + list(trunk) + [(c, None) for c in finals])
 
 
 @torch.no_grad()

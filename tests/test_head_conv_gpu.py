@@ -199,6 +199,32 @@ def test_branches_planted_2_pow_20_apart_keep_their_own_bound():
         assert r <= 1.0, (b, r)
 
 
+# ---- one kernel for two families -------------------------------------------------------------------------------------------
+# 70 pixels: a wave's tile straddles two samples and the last tile is partial; 969: four workgroups, the last one partial
+@pytest.mark.parametrize("B,H,W", [(2, 5, 7), (3, 17, 19)])
+@pytest.mark.parametrize("stage,c", [("shared", 64), ("trunk", 32), ("trunk", 64)])
+def test_the_heads_stages_are_the_bev_layer_bit_for_bit(stage, c, B, H, W):
+    """A Conv 3x3 (stride 1, padding 1) c -> c + BatchNorm + ReLU through ``mssvt_bev_conv`` (run-time taps, one header
+    record) and through the head's shared layer / its one-branch trunk (folded taps, sliced input, a record per slice): the
+    same outputs, the same blob past the first record (which differs in k alone), and the head's epilogue words are the
+    stand-alone exponent pass over the output."""
+    from mssvt_amd import bev_conv
+    conv, bn = make_conv(c, c, seed=c + B, bias=True, wscale=0.1), make_bn(c, seed=c + H)
+    x = torch.randn((B, H, W, c), generator=torch.Generator().manual_seed(W + c)).mul_(3.0).to(DEV)
+    layer = bev_conv.pack(conv, bn)
+    want = bev_conv.conv_bn_act(x.permute(0, 3, 1, 2), layer, relu=True).permute(0, 2, 3, 1)
+    if stage == "shared":
+        packed = head_conv.pack_shared(conv, bn)
+        y, e = head_conv.run_shared(packed, x)
+    else:
+        packed = head_conv.pack_trunk([(conv, bn)])
+        y, e = head_conv.run_trunk(packed, x, head_conv.expmap(x, c))
+    assert y.shape == want.shape and torch.equal(y, want)
+    assert packed.blob.numel() == layer.blob.numel() and torch.equal(packed.blob[16:], layer.blob[16:])
+    assert torch.equal(packed.blob[:8], layer.blob[:8])  # (and of the first record, the two powers of two)
+    assert torch.equal(e, head_conv.expmap(y, c))
+
+
 # ---- geometry ----------------------------------------------------------------------------------------------------------
 def impulses(cin, H=5, W=7):
     """Sample b holds one element 1 + 2^-12 (hi = 1, lo = 2^-12) at position b of the grid: every border and corner."""
