@@ -7,6 +7,7 @@ container.  The .so is git-ignored but travels to the GPU box with the snapshot.
 """
 import glob
 import os
+import re
 import subprocess
 import sys
 
@@ -29,21 +30,28 @@ FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-ffp-contract=o
 # sources under another optimisation level / without the post-RA scheduler.  A result that is "right by the luck of the
 # schedule" (a sum read before its last matrix instruction has landed) differs between them; every
 # variant must reproduce the default library's outputs.  Only the listed files are recompiled, the rest is re-linked.
-# The list is DERIVED (every csrc/*.hip whose text names a matrix instruction), so a new MFMA translation unit cannot be
-# left out; ceiling.hip holds timing-only launches that no output depends on.
+# The list is DERIVED (every csrc/*.hip whose text, or that of a csrc header it includes, names a matrix instruction: the
+# MFMA macros live in split_f16.hip.h), so a new MFMA translation unit cannot be left out; ceiling.hip holds timing-only
+# launches that no output depends on.
 MFMA_EXCLUDED = ("ceiling.hip",)
+_INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
+
+
+def names_mfma(path, seen=None):
+    """Does this csrc file, or a header under csrc/ that it includes (transitively), name a matrix instruction?"""
+    seen = set() if seen is None else seen
+    path = os.path.realpath(path)
+    if path in seen or os.path.dirname(path) != os.path.realpath(CSRC) or not os.path.exists(path):
+        return False
+    seen.add(path)
+    with open(path) as f:
+        text = f.read()
+    return "mfma" in text or any(names_mfma(os.path.join(CSRC, inc), seen) for inc in _INCLUDE.findall(text))
 
 
 def mfma_sources():
-    out = []
-    for src in sorted(glob.glob(os.path.join(CSRC, "*.hip"))):
-        base = os.path.basename(src)
-        if base in MFMA_EXCLUDED:
-            continue
-        with open(src) as f:
-            if "mfma" in f.read():
-                out.append(base)
-    return tuple(out)
+    return tuple(os.path.basename(src) for src in sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+                 if os.path.basename(src) not in MFMA_EXCLUDED and names_mfma(src))
 
 
 MFMA_SOURCES = mfma_sources()

@@ -40,9 +40,7 @@
 //
 // Windows (B) are processed in the plan's work order (heaviest first), dealt round-robin to the
 // wavefronts of a persistent grid.
-#include "common.hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "split_f16.hip.h"
 
 #define ATTN_ROW_WAVES 4  // waves per workgroup of the per-window launch
 // waves per workgroup of the row-tiled launches (q, o): ONE workgroup per CU and head group -- the weights are staged
@@ -87,41 +85,9 @@ struct AttnPack {
     AttnArgs g[ATTN_MAX_GROUPS];
 };
 
-#define MFMA4(acc, av, bv)                                                    \
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
-
-// ---- split-fp16 operands (kv16 form of launch B, see k_attn_kvh) ---------------------------------------------
-// v = hi + 2^-11 lo with hi = fp16(v), lo = fp16((v - hi) 2^11), both rounded toward zero: 22 mantissa bits; a product
-// sum is three v_mfma_f32_16x16x32_f16 (hi hi, hi lo, lo hi) accumulated in fp32 -- the arithmetic of csrc/ffn.hip
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+// ---- split-fp16 operands (kv16 form of launch B, see k_attn_kvh): the arithmetic of split_f16.hip.h, packed-multiply form,
+// both halves rounded toward zero -------------------------------------------------------------------------------
 typedef __fp16 fp16v4 __attribute__((__vector_size__(4 * sizeof(__fp16))));
-#define MFMA_H(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
-#define H16_SCALE 2048.0f
-#define H16_INV (1.0f / 2048.0f)
-__device__ __forceinline__ void h16_split4(const f32x4 v, h16x4 &hi, h16x4 &lo) {
-    const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(v[0], v[1]), b = __builtin_amdgcn_cvt_pkrtz(v[2], v[3]);
-    // (v - hi) 2^11 as fma(hi, -2^11, v 2^11): every step is exact, so the bits are those of the subtraction form, and
-    // the fp16 -> fp32 conversion of hi rides inside the instruction (v_fma_mix_f32): 3 instead of 4 VALU per value
-    const f32x2 s01 = f32x2{v[0], v[1]} * f32x2{H16_SCALE, H16_SCALE}, s23 = f32x2{v[2], v[3]} * f32x2{H16_SCALE, H16_SCALE};  // v_pk_mul_f32
-    const fp16x2 c = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)a[0], -H16_SCALE, s01[0]), __builtin_fmaf((float)a[1], -H16_SCALE, s01[1])),
-                 d = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)b[0], -H16_SCALE, s23[0]), __builtin_fmaf((float)b[1], -H16_SCALE, s23[1]));
-    hi = h16x4{(_Float16)a[0], (_Float16)a[1], (_Float16)b[0], (_Float16)b[1]};
-    lo = h16x4{(_Float16)c[0], (_Float16)c[1], (_Float16)d[0], (_Float16)d[1]};
-}
-__device__ __forceinline__ h16x8 h16_cat(const h16x4 a, const h16x4 b) {
-    return h16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
-// (hi, lo) fragments of 8 values held as two accumulator-layout quads
-__device__ __forceinline__ void h16_split8(const f32x4 v0, const f32x4 v1, h16x8 &hi, h16x8 &lo) {
-    h16x4 h0, l0, h1, l1;
-    h16_split4(v0, h0, l0);
-    h16_split4(v1, h1, l1);
-    hi = h16_cat(h0, h1);
-    lo = h16_cat(l0, l1);
-}
 // kv16 operand order: k slot (g, j) of a 32-wide step P <-> index 32 P + 16 (j / 4) + 4 g + j % 4 -- what a lane holds after
 // two DENSE 16-byte row pieces S = 2 P, 2 P + 1 (piece S of lane (., g) = indices 16 S + 4 g .. + 3: the four g lanes of a
 // row read 64 contiguous bytes), and equally the accumulator registers of two consecutive 16-row output tiles
@@ -281,7 +247,7 @@ __global__ void __launch_bounds__(ATTN_QO_WAVES *MSSVT_WAVE) k_attn_q(AttnPack p
 #pragma unroll
                 for (int P = 0; P < NT / 2; ++P) {
                     h16x8 hi, lo;
-                    h16_split8(acc[2 * P] * a.scale, acc[2 * P + 1] * a.scale, hi, lo);
+                    split8_rtz(acc[2 * P] * a.scale, acc[2 * P + 1] * a.scale, hi, lo);
                     if (row_ok) {
                         dsth[(P * 4 + g) * 2] = hi;
                         dsth[(P * 4 + g) * 2 + 1] = lo;
@@ -432,7 +398,6 @@ __global__ void __launch_bounds__(ATTN_QO_WAVES *MSSVT_WAVE) k_attn_o(AttnPack p
 //   WkF2 [p][u][hi | lo][lane] x 16 B  WkF (x log2 e) of heads 2 p (j < 4) and 2 p + 1 (j >= 4) side by side: one K = 32 instruction
 //                                      per head PAIR in k_attn_kvh<.., QP> (its B operand is zero outside the column's head)
 #define ATTN_QO16_WAVES 8
-#define MFMA_H16(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x16f16((av), (bv), acc, 0, 0, 0)
 template <int CG>
 struct AttnBlob {
     static constexpr int NT = CG / 16, NP = CG / 32;
@@ -456,7 +421,7 @@ __global__ void __launch_bounds__(MSSVT_WAVE) k_attn_pack(const float *Wq, const
 #pragma unroll
         for (int j = 0; j < 4; ++j) v[j] = Wkv[(size_t)(16 * h + 4 * g + j) * CG + (16 * u + m)] * scale;
         h16x4 hi, lo;
-        h16_split4(v, hi, lo);
+        split4_rtz(v, hi, lo);
         h16x4 *dst = reinterpret_cast<h16x4 *>(blob + L::WK) + (size_t)f * 2 * 64 + lane;
         dst[0] = hi;
         dst[64] = lo;
@@ -473,7 +438,7 @@ __global__ void __launch_bounds__(MSSVT_WAVE) k_attn_pack(const float *Wq, const
             v1[j] = Wkv[(size_t)(16 * (2 * pr + 1) + 4 * g + j) * CG + (16 * u + m)] * (scale * 1.4426950408889634f);
         }
         h16x8 hi, lo;
-        h16_split8(v0, v1, hi, lo);
+        split8_rtz(v0, v1, hi, lo);
         h16x8 *dst = reinterpret_cast<h16x8 *>(blob + L::WK2) + (size_t)f * 2 * 64 + lane;
         dst[0] = hi;
         dst[64] = lo;
@@ -485,7 +450,7 @@ __global__ void __launch_bounds__(MSSVT_WAVE) k_attn_pack(const float *Wq, const
         const float *rowp = Wkv + (size_t)(CG + 16 * t + m) * CG + 32 * P + 16 * (g & 1) + 4 * (g >> 1);
         const float4 w0 = *reinterpret_cast<const float4 *>(rowp), w1 = *reinterpret_cast<const float4 *>(rowp + 8);
         h16x8 hi, lo;
-        h16_split8(f32x4{w0.x, w0.y, w0.z, w0.w}, f32x4{w1.x, w1.y, w1.z, w1.w}, hi, lo);
+        split8_rtz(f32x4{w0.x, w0.y, w0.z, w0.w}, f32x4{w1.x, w1.y, w1.z, w1.w}, hi, lo);
         h16x8 *dst = reinterpret_cast<h16x8 *>(blob + L::WV2) + (size_t)f * 2 * 64 + lane;
         dst[0] = hi;
         dst[64] = lo;
@@ -496,7 +461,7 @@ __global__ void __launch_bounds__(MSSVT_WAVE) k_attn_pack(const float *Wq, const
                                                                                   : Wo + (size_t)(16 * t + m) * CG) + 32 * P + 4 * g;
     const float4 w0 = *reinterpret_cast<const float4 *>(rowp), w1 = *reinterpret_cast<const float4 *>(rowp + 16);
     h16x8 hi, lo;
-    h16_split8(f32x4{w0.x, w0.y, w0.z, w0.w}, f32x4{w1.x, w1.y, w1.z, w1.w}, hi, lo);
+    split8_rtz(f32x4{w0.x, w0.y, w0.z, w0.w}, f32x4{w1.x, w1.y, w1.z, w1.w}, hi, lo);
     h16x8 *dst = reinterpret_cast<h16x8 *>(blob + (which == 0 ? L::WQ : which == 2 ? L::WV : L::WO)) + (size_t)f * 2 * 64 + lane;
     dst[0] = hi;
     dst[64] = lo;
@@ -592,7 +557,7 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_q16(Att
 #pragma unroll
                 for (int i = 0; i < 4; ++i) xq[2 * P + h][i] += fmaxf(p1[i], 0.0f);
             }
-            h16_split8(xq[2 * P], xq[2 * P + 1], xh[P], xl[P]);
+            split8_rtz(xq[2 * P], xq[2 * P + 1], xh[P], xl[P]);
         }
         __builtin_amdgcn_sched_barrier(0);
         // GEMM1^T: Q'^T[o][row] = sum_c Wq[o][c] xq[row][c] + bq[o]; accumulator (row, g), i <-> o = 16 t + 4 g + i
@@ -608,8 +573,8 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_q16(Att
                 MFMA_H(cr, wh, xl[P]);
                 MFMA_H(cr, wl, xh[P]);
             }
-            h16_split4(f32x4{__builtin_fmaf(cr[0], H16_INV, mm[0]), __builtin_fmaf(cr[1], H16_INV, mm[1]),
-                             __builtin_fmaf(cr[2], H16_INV, mm[2]), __builtin_fmaf(cr[3], H16_INV, mm[3])}, qh[t], ql[t]);
+            split4_rtz(f32x4{__builtin_fmaf(cr[0], SPLIT_INV, mm[0]), __builtin_fmaf(cr[1], SPLIT_INV, mm[1]),
+                             __builtin_fmaf(cr[2], SPLIT_INV, mm[2]), __builtin_fmaf(cr[3], SPLIT_INV, mm[3])}, qh[t], ql[t]);
             if (t & 1) __builtin_amdgcn_sched_barrier(0);
         }
         const bool row_ok = tile * 16 + r < rows;
@@ -618,7 +583,7 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_q16(Att
             h16x8 *dq = reinterpret_cast<h16x8 *>(dst);
 #pragma unroll
             for (int t = 0; t < NT; ++t)
-                if (row_ok) dq[t * 4 + g] = h16_cat(qh[t], ql[t]);
+                if (row_ok) dq[t * 4 + g] = split_cat(qh[t], ql[t]);
             continue;
         }
         // GEMM2^T per head (= tile h): Qt_h^T[c][row] = sum_{o in head h} (scale Wk[o][c]) Q'[row][o]
@@ -636,12 +601,12 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_q16(Att
                     MFMA_H16(cr, wh, ql[h]);
                     MFMA_H16(cr, wl, qh[h]);
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) acc[e][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
+                    for (int i = 0; i < 4; ++i) acc[e][i] = __builtin_fmaf(cr[i], SPLIT_INV, mm[i]);
                 }
                 if (OUT == 1) {
                     h16x8 *dsth = reinterpret_cast<h16x8 *>(dst + h * CG);
                     h16x8 hi, lo;
-                    h16_split8(acc[0], acc[1], hi, lo);
+                    split8_rtz(acc[0], acc[1], hi, lo);
                     if (row_ok) {
                         dsth[(P * 4 + g) * 2] = hi;
                         dsth[(P * 4 + g) * 2 + 1] = lo;
@@ -704,14 +669,14 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_o16(Att
 #pragma unroll
             for (int P = 0; P < NP; ++P) {
                 h16x8 xh, xl;
-                h16_split8(x[2 * P], x[2 * P + 1], xh, xl);
+                split8_rtz(x[2 * P], x[2 * P + 1], xh, xl);
                 const h16x8 wh = WvF[((t * NP + P) * 2) * 64 + lane], wl = WvF[((t * NP + P) * 2 + 1) * 64 + lane];
                 MFMA_H(mm, wh, xh);
                 MFMA_H(cr, wh, xl);
                 MFMA_H(cr, wl, xh);
             }
 #pragma unroll
-            for (int i = 0; i < 4; ++i) v[t][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
+            for (int i = 0; i < 4; ++i) v[t][i] = __builtin_fmaf(cr[i], SPLIT_INV, mm[i]);
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int S = 0; S < NT; ++S) x[S] = xn[S];
@@ -719,7 +684,7 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_o16(Att
         // GEMM4^T: out^T[p][row] = sum_o Wo[p][o] V[row][o] + bo[p]; two V tiles = one 32-wide step of the B operand
         h16x8 vh[NP], vl[NP];
 #pragma unroll
-        for (int s = 0; s < NP; ++s) h16_split8(v[2 * s], v[2 * s + 1], vh[s], vl[s]);
+        for (int s = 0; s < NP; ++s) split8_rtz(v[2 * s], v[2 * s + 1], vh[s], vl[s]);
         float *dst = a.attn + (size_t)dest * a.C + a.c0 + 4 * g;
 #pragma unroll
         for (int u = 0; u < NT; ++u) {
@@ -733,8 +698,8 @@ __global__ void __launch_bounds__(ATTN_QO16_WAVES *MSSVT_WAVE, 4) k_attn_o16(Att
                 MFMA_H(cr, wl, vh[s]);
             }
             if (row_ok)
-                *reinterpret_cast<float4 *>(dst + 16 * u) = make_float4(__builtin_fmaf(cr[0], H16_INV, mm[0]), __builtin_fmaf(cr[1], H16_INV, mm[1]),
-                                                                        __builtin_fmaf(cr[2], H16_INV, mm[2]), __builtin_fmaf(cr[3], H16_INV, mm[3]));
+                *reinterpret_cast<float4 *>(dst + 16 * u) = make_float4(__builtin_fmaf(cr[0], SPLIT_INV, mm[0]), __builtin_fmaf(cr[1], SPLIT_INV, mm[1]),
+                                                                        __builtin_fmaf(cr[2], SPLIT_INV, mm[2]), __builtin_fmaf(cr[3], SPLIT_INV, mm[3]));
             if (u & 1) __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -1252,7 +1217,7 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
 #pragma unroll
                         for (int i = 0; i < 4; ++i) tk[h][i] = T1n[t][u][i] + fmaxf(p1[i], 0.0f);
                     }
-                    h16_split8(tk[0], tk[1], th, tl);
+                    split8_rtz(tk[0], tk[1], th, tl);
                 }
                 char *dst = Ti + (16 * t + la) * RS + 64 * P + 16 * g;  // key row 16 t + la, the lane's 8 k slots of step P
                 *reinterpret_cast<h16x8 *>(dst) = th;
@@ -1319,16 +1284,16 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
 #pragma unroll
                             for (int pr = 0; pr < NH / 2; ++pr) {  // heads 2 pr | 2 pr + 1 in the two halves of the k slots
                                 const h16x8 wh = WkF2[((pr * NT + u) * 2) * 64 + lane], wl = WkF2[((pr * NT + u) * 2 + 1) * 64 + lane];
-                                const h16x8 sh = h16_cat(hh == 2 * pr ? bh : z4, hh == 2 * pr + 1 ? bh : z4),
-                                            sl = h16_cat(hh == 2 * pr ? bl : z4, hh == 2 * pr + 1 ? bl : z4);
+                                const h16x8 sh = split_cat(hh == 2 * pr ? bh : z4, hh == 2 * pr + 1 ? bh : z4),
+                                            sl = split_cat(hh == 2 * pr ? bl : z4, hh == 2 * pr + 1 ? bl : z4);
                                 MFMA_H(mm, wh, sh);
                                 MFMA_H(cr, wh, sl);
                                 MFMA_H(cr, wl, sh);
                             }
 #pragma unroll
-                            for (int i = 0; i < 4; ++i) qt[e][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
+                            for (int i = 0; i < 4; ++i) qt[e][i] = __builtin_fmaf(cr[i], SPLIT_INV, mm[i]);
                         }
-                        h16_split8(qt[0], qt[1], qh[P], ql[P]);
+                        split8_rtz(qt[0], qt[1], qh[P], ql[P]);
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -1348,7 +1313,7 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
                         MFMA_H(cr, tl, qh[P]);
                     }
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) sc[t][i] = __builtin_fmaf(cr[i], H16_INV, mm[i]);
+                    for (int i = 0; i < 4; ++i) sc[t][i] = __builtin_fmaf(cr[i], SPLIT_INV, mm[i]);
                 }
                 // softmax over the unmasked keys in base 2 (QP: log2 e is folded into the Wk fragments): masked slots score -inf
                 float mx = -INFINITY;
@@ -1379,12 +1344,12 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
                 h16x8 ph[LS], pl[LS];
                 if constexpr (LT == 1) {  // the step's second tile: P = 0 and zero tokens, as registers
                     h16x4 h0, l0;
-                    h16_split4(sc[0] * inv, h0, l0);
-                    ph[0] = h16_cat(h0, z4);
-                    pl[0] = h16_cat(l0, z4);
+                    split4_rtz(sc[0] * inv, h0, l0);
+                    ph[0] = split_cat(h0, z4);
+                    pl[0] = split_cat(l0, z4);
                 } else {
 #pragma unroll
-                    for (int s = 0; s < LS; ++s) h16_split8(sc[2 * s] * inv, sc[2 * s + 1] * inv, ph[s], pl[s]);
+                    for (int s = 0; s < LS; ++s) split8_rtz(sc[2 * s] * inv, sc[2 * s + 1] * inv, ph[s], pl[s]);
                 }
 #pragma unroll
                 for (int u = 0; u < NT; ++u) {
@@ -1392,14 +1357,14 @@ __global__ void __launch_bounds__(ATTN_ROW_WAVES *MSSVT_WAVE, KT <= 2 ? (QP || C
 #pragma unroll
                     for (int s = 0; s < LS; ++s) {
                         const char *blk = tr_base + 32 * s * RS + 32 * u;
-                        const h16x8 ah = h16_cat(lds_read_tr16(blk), LT == 1 ? z4 : lds_read_tr16(blk + 16 * RS));
-                        const h16x8 al = h16_cat(lds_read_tr16(blk + IMG), LT == 1 ? z4 : lds_read_tr16(blk + IMG + 16 * RS));
+                        const h16x8 ah = split_cat(lds_read_tr16(blk), LT == 1 ? z4 : lds_read_tr16(blk + 16 * RS));
+                        const h16x8 al = split_cat(lds_read_tr16(blk + IMG), LT == 1 ? z4 : lds_read_tr16(blk + IMG + 16 * RS));
                         MFMA_H(mm, ah, ph[s]);
                         MFMA_H(cr, ah, pl[s]);
                         MFMA_H(cr, al, ph[s]);
                     }
-                    const f32x4 xt = f32x4{__builtin_fmaf(cr[0], H16_INV, mm[0]), __builtin_fmaf(cr[1], H16_INV, mm[1]),
-                                           __builtin_fmaf(cr[2], H16_INV, mm[2]), __builtin_fmaf(cr[3], H16_INV, mm[3])};
+                    const f32x4 xt = f32x4{__builtin_fmaf(cr[0], SPLIT_INV, mm[0]), __builtin_fmaf(cr[1], SPLIT_INV, mm[1]),
+                                           __builtin_fmaf(cr[2], SPLIT_INV, mm[2]), __builtin_fmaf(cr[3], SPLIT_INV, mm[3])};
                     if (q_ok) {  // xbar replaces qt in place (this lane's own bytes of the row)
                         // image column 16 u + 4 g + i is k slot (2 (u % 2) + g / 2, 4 (g % 2) + i) of step u / 2 (see above)
                         store_handoff(xrow + 32 * (u >> 1) + 16 * (g & 1) + 8 * (u & 1) + 4 * (g >> 1), xt);

@@ -23,9 +23,8 @@
 // IS, after conversion, the operand of the next product over its row index -- no shuffle, no LDS round trip --
 // and 4 consecutive channels of a row are one 16-byte global load.  The weight matrices sit in LDS as ready
 // fragments [matrix][tile n][step s][lane] x 16 bytes (one conflict-free ds_read_b128 per MFMA operand).
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 #define BA_WAVES 4
@@ -55,7 +54,6 @@ __device__ __forceinline__ bf16x8 pack8(const f32x4 lo, const f32x4 hi) {
     return r;
 }
 #define MFMA_BF(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16((av), (bv), acc, 0, 0, 0)
-#define MFMA_F4(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
 
 #ifdef MSSVT_STAMPS  // developer instrumentation: cycles per phase, summed per wave (first 64 workgroups, group 0)
 __device__ unsigned long long g_attn_bf_stamps[64 * BA_WAVES * 8];
@@ -227,7 +225,7 @@ __global__ void __launch_bounds__(BA_WAVES *MSSVT_WAVE, KT >= 4 ? 1 : 2) k_attn_
                 tk[u] = Z4;
                 if (u < NT) {
                     f32x4 p1 = Z4;
-                    MFMA_F4(p1, wu[u], rel_r[t]);
+                    MFMA4(p1, wu[u], rel_r[t]);
 #pragma unroll
                     for (int i = 0; i < 4; ++i) tk[u][i] = T1n[t][u][i] + fmaxf(p1[i], 0.0f);
                 }
@@ -333,7 +331,7 @@ __global__ void __launch_bounds__(BA_WAVES *MSSVT_WAVE, KT >= 4 ? 1 : 2) k_attn_
                     tk[u] = Z4;
                     if (u < NT) {
                         f32x4 p1 = Z4;
-                        MFMA_F4(p1, wu[u], qrel);
+                        MFMA4(p1, wu[u], qrel);
 #pragma unroll
                         for (int i = 0; i < 4; ++i) tk[u][i] = xq[u][i] + fmaxf(p1[i], 0.0f);
                     }

@@ -10,10 +10,8 @@
 // beside the kernel's own time: the gap between the two is what the dependency chain (rows -> LDS -> product -> LDS ->
 // product -> rows; tokens -> image -> scores -> softmax -> second product) costs, the gap to the HBM roof is what the mix
 // itself costs.  ("Next round" item 1.)
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
 
 // NV independent fused multiply-adds per lane, eight chains (a chain's dependent latency is hidden by the others)
 template <int NV>

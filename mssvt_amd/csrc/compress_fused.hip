@@ -19,16 +19,13 @@
 // activations, lane (row = l % 16, g = l / 16) -> channels 16 S + 4 g + j = 16-byte global accesses),
 // weights resident in LDS for the whole launch, no barrier after staging.
 // Masked list slots carry an additive -100 in the reference (relative weight <= e^-100): skipped.
-#include "common.hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+#include "split_f16.hip.h"
 
 // waves per workgroup: ONE workgroup per CU (the 66 KiB weight matrix is staged once per CU; two 8-wave workgroups do
 // not fit beside the per-wave window lists), as many waves as the registers allow
 #define CFQ_NW 12  // k_cmp_query_keys (<= 168 VGPRs)
 #define CFK_NW 12  // k_cmp_kv
 #define CFO_NW 16  // k_cmp_out (<= 128 VGPRs)
-#define MFMA4(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
 
 struct CmpArgs {
     int C, ns, num_voxels;
@@ -94,28 +91,12 @@ __device__ __forceinline__ void cf_gemm(f32x4 (&acc)[NT], const float *W_l, cons
     }
 }
 
-// ---- the same products with every fp32 operand split into two fp16 halves (22 of 24 mantissa bits) (see ffn.hip, k_ffn_ws): hi =
-// fp16(v), lo = fp16((v - hi) 2^11); sum a b = sum a_hi b_hi + 2^-11 (sum a_hi b_lo + sum a_lo b_hi), three
-// v_mfma_f32_16x16x32_f16 with fp32 accumulation: the fp32 instruction's error against float64 at 3/16 of its cycles.
+// ---- the same products with every fp32 operand split into two fp16 halves (split_f16.hip.h; split4_rtz_scalar: the
+// scalar-multiply form, both halves rounded toward zero).
 // LDS row of a weight matrix: C halves hi | C halves lo (+ 16 bytes: the same (C + 4)-float stride, conflict free);
 // inside a 32-channel group channel 16 h + 4 g + j sits at half 8 g + 4 h + j, so that lane (row, g) reads its 8 k
 // slots as one ds_read_b128 and the B operand is just the split of x[2 P] | x[2 P + 1] (lane (row, g): channels
 // 32 P + 4 g + j and 32 P + 16 + 4 g + j).  The caller guarantees the fp16 range of the operands (fused.py).
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-#define CF_SCALE 2048.0f
-#define CF_INV (1.0f / 2048.0f)
-
-__device__ __forceinline__ void cf_split4(const float v0, const float v1, const float v2, const float v3, h16x4 &hi, h16x4 &lo) {
-    const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(v0, v1), b = __builtin_amdgcn_cvt_pkrtz(v2, v3);
-    // (v - hi) 2^11 as fma(hi, -2^11, v 2^11): exact steps, same bits, hi converted inside v_fma_mix_f32
-    const fp16x2 c = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)a[0], -CF_SCALE, v0 * CF_SCALE), __builtin_fmaf((float)a[1], -CF_SCALE, v1 * CF_SCALE));
-    const fp16x2 d = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)b[0], -CF_SCALE, v2 * CF_SCALE), __builtin_fmaf((float)b[1], -CF_SCALE, v3 * CF_SCALE));
-    hi = h16x4{(_Float16)a[0], (_Float16)a[1], (_Float16)b[0], (_Float16)b[1]};
-    lo = h16x4{(_Float16)c[0], (_Float16)c[1], (_Float16)d[0], (_Float16)d[1]};
-}
-
 template <int COLS, int LS>
 __device__ __forceinline__ void cf_stage_h(float *dst, const float *src, int rows) {
     constexpr int UN = 8;
@@ -134,7 +115,7 @@ __device__ __forceinline__ void cf_stage_h(float *dst, const float *src, int row
                 const int c = e % COLS, c32 = c & 31;  // c32 = 16 h + 4 g (a float4 never straddles a group of 4)
                 const int half = (c - c32) + 8 * ((c32 >> 2) & 3) + 4 * (c32 >> 4);
                 h16x4 hi, lo;
-                cf_split4(v[u].x, v[u].y, v[u].z, v[u].w, hi, lo);
+                split4_rtz_scalar(v[u].x, v[u].y, v[u].z, v[u].w, hi, lo);
                 _Float16 *row = reinterpret_cast<_Float16 *>(dst + (size_t)(e / COLS) * LS);
                 *reinterpret_cast<h16x4 *>(row + half) = hi;
                 *reinterpret_cast<h16x4 *>(row + COLS + half) = lo;
@@ -151,8 +132,8 @@ __device__ __forceinline__ void cf_gemm_h(f32x4 (&acc)[NT], const float *W_l, co
 #pragma unroll
     for (int P = 0; P < NP; ++P) {
         h16x4 h0, l0, h1, l1;
-        cf_split4(x[2 * P][0], x[2 * P][1], x[2 * P][2], x[2 * P][3], h0, l0);
-        cf_split4(x[2 * P + 1][0], x[2 * P + 1][1], x[2 * P + 1][2], x[2 * P + 1][3], h1, l1);
+        split4_rtz_scalar(x[2 * P][0], x[2 * P][1], x[2 * P][2], x[2 * P][3], h0, l0);
+        split4_rtz_scalar(x[2 * P + 1][0], x[2 * P + 1][1], x[2 * P + 1][2], x[2 * P + 1][3], h1, l1);
         xh[P] = h16x8{h0[0], h0[1], h0[2], h0[3], h1[0], h1[1], h1[2], h1[3]};
         xl[P] = h16x8{l0[0], l0[1], l0[2], l0[3], l1[0], l1[1], l1[2], l1[3]};
     }
@@ -182,7 +163,7 @@ __device__ __forceinline__ void cf_gemm_h(f32x4 (&acc)[NT], const float *W_l, co
 #pragma unroll
         for (int u = 0; u < UG; ++u)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) acc[u0 + u][i] = __builtin_fmaf(lo[u][i], CF_INV, acc[u0 + u][i]);
+            for (int i = 0; i < 4; ++i) acc[u0 + u][i] = __builtin_fmaf(lo[u][i], SPLIT_INV, acc[u0 + u][i]);
     }
 }
 

@@ -8,7 +8,7 @@
 // queries between its three launches (308 MB of HBM traffic against ~60 MB of input + output) and walks every window's list
 // twice with one dependent load per slot.
 //
-// One workgroup of C / 16 waves per CU; wave w keeps, as split-fp16 MFMA A-fragments (see ffn.hip, k_ffn_ws) in REGISTERS for
+// One workgroup of C / 16 waves per CU; wave w keeps, as split-fp16 MFMA A-fragments (split_f16.hip.h) in REGISTERS for
 // the whole launch, rows [16 w, 16 w + 16) of pos_proj.2, Wk and Wv -- i.e. everything of HEAD w -- and reads its rows of
 // Wq and Wo from LDS (used once per 16 windows).  The workgroup owns a CHUNK: consecutive windows = consecutive rows holding
 // 1 / gridDim of the cost (rows and windows weighed 8 : 5), found by 4096 probes of pair_win -- or handed in (CwArgs::ends).  The chunk is walked as a
@@ -30,19 +30,9 @@
 // row order, the carried piece as its prefix) does not depend on where the pieces or the chunks are cut -- a scene's rows are
 // bit-identical whatever it shares a batch with.  Differences to compress_fused.hip: summation order of the softmax (row
 // order instead of list-slot order), 2^x instead of e^x, rcp instead of a division -- rounding only.
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-
-#define CW_SCALE 2048.0f
-#define CW_INV (1.0f / 2048.0f)
 #define CW_LOG2E 1.4426950408889634f
-#define MFMA_H(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
-#define MFMA4(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
 #define CW_MATS 5  // packed order: pos_proj.2, Wk, Wv (registers) | Wq, Wo (LDS)
 
 struct CwArgs {
@@ -70,15 +60,7 @@ __device__ __forceinline__ float cw_centre(int idx, float cell, float lo) {
     return __fadd_rn(__fmul_rn(__fadd_rn((float)idx, 0.5f), cell), lo);  // ref with_coords, mssvt_backbone.py:132-137
 }
 
-// v -> (hi, lo): hi = fp16(v), lo = fp16((v - hi) 2^11), round toward zero (the arithmetic of ffn.hip)
-__device__ __forceinline__ void cw_split4(const float v0, const float v1, const float v2, const float v3, h16x4 &hi, h16x4 &lo) {
-    const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(v0, v1), b = __builtin_amdgcn_cvt_pkrtz(v2, v3);
-    const fp16x2 c = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)a[0], -CW_SCALE, v0 * CW_SCALE), __builtin_fmaf((float)a[1], -CW_SCALE, v1 * CW_SCALE));
-    const fp16x2 d = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)b[0], -CW_SCALE, v2 * CW_SCALE), __builtin_fmaf((float)b[1], -CW_SCALE, v3 * CW_SCALE));
-    hi = h16x4{(_Float16)a[0], (_Float16)a[1], (_Float16)b[0], (_Float16)b[1]};
-    lo = h16x4{(_Float16)c[0], (_Float16)c[1], (_Float16)d[0], (_Float16)d[1]};
-}
-__device__ __forceinline__ h16x8 cw_cat(const h16x4 a, const h16x4 b) { return h16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}; }
+// (operands: split4_rtz_scalar of split_f16.hip.h -- the scalar-multiply form, both halves rounded toward zero)
 
 // order-preserving float <-> int (signed compare): the channel-wise max goes through ds_max_i32
 __device__ __forceinline__ int cw_key(float v) {
@@ -107,10 +89,10 @@ __global__ void __launch_bounds__(MSSVT_WAVE) k_cmp_ws_pack(const float *Wp2, co
         const float *src = W + (size_t)(16 * wv + la) * C + 32 * P + 4 * g;
         const float4 v0 = *reinterpret_cast<const float4 *>(src), v1 = *reinterpret_cast<const float4 *>(src + 16);
         h16x4 h0, l0, h1, l1;
-        cw_split4(v0.x, v0.y, v0.z, v0.w, h0, l0);
-        cw_split4(v1.x, v1.y, v1.z, v1.w, h1, l1);
-        dst[(P * 2) * 64] = cw_cat(h0, h1);
-        dst[(P * 2 + 1) * 64] = cw_cat(l0, l1);
+        split4_rtz_scalar(v0.x, v0.y, v0.z, v0.w, h0, l0);
+        split4_rtz_scalar(v1.x, v1.y, v1.z, v1.w, h1, l1);
+        dst[(P * 2) * 64] = split_cat(h0, h1);
+        dst[(P * 2 + 1) * 64] = split_cat(l0, l1);
     }
 }
 
@@ -373,7 +355,7 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
             {                 // q_tok, this wave's 16 channels of the 16 windows -> B fragments (in the K / V fragments' place)
                 const int4 k0 = *reinterpret_cast<const int4 *>(qmax + CW_QSLOT(la, ch));
                 h16x4 hi, lo;
-                cw_split4(cw_unkey(k0.x), cw_unkey(k0.y), cw_unkey(k0.z), cw_unkey(k0.w), hi, lo);
+                split4_rtz_scalar(cw_unkey(k0.x), cw_unkey(k0.y), cw_unkey(k0.z), cw_unkey(k0.w), hi, lo);
                 reinterpret_cast<h16x4 *>(kfrag + (ks * 2) * 64 + lane)[hs] = hi;
                 reinterpret_cast<h16x4 *>(kfrag + (ks * 2 + 1) * 64 + lane)[hs] = lo;
             }
@@ -395,7 +377,7 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
                 }
                 qpA = qpB;
 #pragma unroll
-                for (int i = 0; i < 4; ++i) qpB[i] = __builtin_fmaf(l[i] + k[i], CW_INV, m[i]) * a.qscale;
+                for (int i = 0; i < 4; ++i) qpB[i] = __builtin_fmaf(l[i] + k[i], SPLIT_INV, m[i]) * a.qscale;
 #ifdef CW_DEBUG
                 if (gw0 + la < gw1 && g_cw_dbg[1])
                     for (int i = 0; i < 4; ++i) g_cw_dbg[1][(size_t)(gw0 + la) * C + ch + i] = qpB[i];
@@ -423,7 +405,7 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
             MFMA4(p, w1a0, in0);
             MFMA4(p, w1a1, in1);
             h16x4 hi, lo;
-            cw_split4(fmaxf(p[0], 0.f), fmaxf(p[1], 0.f), fmaxf(p[2], 0.f), fmaxf(p[3], 0.f), hi, lo);
+            split4_rtz_scalar(fmaxf(p[0], 0.f), fmaxf(p[1], 0.f), fmaxf(p[2], 0.f), fmaxf(p[3], 0.f), hi, lo);
             reinterpret_cast<h16x4 *>(hfrag + (ks * 2) * 64 + lane)[hs] = hi;
             reinterpret_cast<h16x4 *>(hfrag + (ks * 2 + 1) * 64 + lane)[hs] = lo;
         }
@@ -441,8 +423,8 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
                 MFMA_H(k, Wpl[P], bh);
             }
             h16x4 hi, lo;
-            cw_split4(xs.x + fmaxf(__builtin_fmaf(l[0] + k[0], CW_INV, m[0]), 0.f), xs.y + fmaxf(__builtin_fmaf(l[1] + k[1], CW_INV, m[1]), 0.f),
-                      xs.z + fmaxf(__builtin_fmaf(l[2] + k[2], CW_INV, m[2]), 0.f), xs.w + fmaxf(__builtin_fmaf(l[3] + k[3], CW_INV, m[3]), 0.f), hi, lo);
+            split4_rtz_scalar(xs.x + fmaxf(__builtin_fmaf(l[0] + k[0], SPLIT_INV, m[0]), 0.f), xs.y + fmaxf(__builtin_fmaf(l[1] + k[1], SPLIT_INV, m[1]), 0.f),
+                      xs.z + fmaxf(__builtin_fmaf(l[2] + k[2], SPLIT_INV, m[2]), 0.f), xs.w + fmaxf(__builtin_fmaf(l[3] + k[3], SPLIT_INV, m[3]), 0.f), hi, lo);
             reinterpret_cast<h16x4 *>(kfrag + (ks * 2) * 64 + lane)[hs] = hi;
             reinterpret_cast<h16x4 *>(kfrag + (ks * 2 + 1) * 64 + lane)[hs] = lo;
         }
@@ -486,8 +468,8 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
             float o[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
-                sc = __builtin_fmaf(__builtin_fmaf(kl[i] + kk[i], CW_INV, km[i]), qr[i], sc);
-                o[i] = __builtin_fmaf(vl[i] + vk[i], CW_INV, vm[i]);
+                sc = __builtin_fmaf(__builtin_fmaf(kl[i] + kk[i], SPLIT_INV, km[i]), qr[i], sc);
+                o[i] = __builtin_fmaf(vl[i] + vk[i], SPLIT_INV, vm[i]);
             }
             sc += lane_xor16(sc);
             sc += lane_xor32(sc);
@@ -575,7 +557,7 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
             const int pend = rvalid && wend ? grow : -1;
             const float inv = __builtin_amdgcn_rcpf(s_);  // (1 ulp; the three-launch form divides)
             h16x4 hi, lo;
-            cw_split4(o01[0] * inv, o01[1] * inv, o23[0] * inv, o23[1] * inv, hi, lo);
+            split4_rtz_scalar(o01[0] * inv, o01[1] * inv, o23[0] * inv, o23[1] * inv, hi, lo);
             for (;;) {
                 const bool mine = pend == jo;
                 if (mine) {
@@ -599,8 +581,8 @@ __global__ void __launch_bounds__((C / 16) * MSSVT_WAVE, 1) k_cmp_ws(CwArgs a, c
                         MFMA_H(k, al, bh);
                     }
                     // (formed before the predicated store: no branch between the products and the reads of their sums)
-                    const float4 res = make_float4(__builtin_fmaf(l[0] + k[0], CW_INV, m[0]), __builtin_fmaf(l[1] + k[1], CW_INV, m[1]),
-                                                   __builtin_fmaf(l[2] + k[2], CW_INV, m[2]), __builtin_fmaf(l[3] + k[3], CW_INV, m[3]));
+                    const float4 res = make_float4(__builtin_fmaf(l[0] + k[0], SPLIT_INV, m[0]), __builtin_fmaf(l[1] + k[1], SPLIT_INV, m[1]),
+                                                   __builtin_fmaf(l[2] + k[2], SPLIT_INV, m[2]), __builtin_fmaf(l[3] + k[3], SPLIT_INV, m[3]));
                     __builtin_amdgcn_sched_barrier(0);
                     if (ow0 + la < ow1) *reinterpret_cast<float4 *>(a.out + (size_t)(ow0 + la) * C + ch) = res;
                 }

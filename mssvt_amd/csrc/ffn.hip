@@ -16,9 +16,8 @@
 //
 // HBM access is fully coalesced although the MFMA operand layouts are not: rows are loaded and stored as whole rows
 // (float4 per lane) and re-laid out on chip.
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 
 struct FfnArgs {
@@ -65,7 +64,6 @@ extern "C" int mssvt_debug_read_stamps(unsigned long long *host) {
 #endif
 #define FFS_NW 8  // waves per workgroup of the split kernels (2 per SIMD, up to 256 VGPRs each)
 
-#define MFMA4(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
 
 // Residual input of one row: x = tab.x < 0 ? 2 x_in : x_in + sum_i w_i attn[row_i]  (table form), or
 // x_new / 2 x_in by owner.  Four row pointers + weights; every stream is read with the same pattern.
@@ -473,46 +471,19 @@ __global__ void __launch_bounds__(FFS_NW *MSSVT_WAVE) k_ffn_down(FfnArgs a, cons
 // interval has one MFMA phase and one row-wise phase: two barriers per tile.  (First version: split-K over
 // the hidden units in GEMM2 with the FF/32 partial tiles summed through LDS -- 128 more VALU instructions per wave
 // and tile for the partial epilogues than the third barrier costs; the phases are VALU-issue bound, not MFMA bound.)
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x4 __attribute__((ext_vector_type(4)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-#define MFMA_H(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
-#define FFW_SCALE 2048.0f
-#define FFW_INV (1.0f / 2048.0f)
+// The operands are split as split_f16.hip.h describes (packed-multiply form, both halves rounded toward zero).
 
 // Row-wise arithmetic on PAIRS: the phases between the matrix products are VALU-issue bound (~350 vector instructions per
 // wave and 16-row tile against 48 MFMAs), and v_pk_mul / v_pk_add / v_pk_fma_f32 do two lanes' worth of the same IEEE
 // operation per issue slot.  Same operations in the same order per element: results are bit-identical to the scalar form.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ f32x2 pk2(float a, float b) { return f32x2{a, b}; }
 __device__ __forceinline__ f32x2 pk1(float a) { return f32x2{a, a}; }
 __device__ __forceinline__ f32x2 pk_fma(f32x2 a, f32x2 b, f32x2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ f32x2 ffw_relu2(f32x2 v) { return f32x2{fmaxf(v[0], 0.f), fmaxf(v[1], 0.f)}; }
 
-// v -> (hi, lo) halves of 4 floats
-__device__ __forceinline__ void ffw_split4(const f32x2 v01, const f32x2 v23, h16x4 &hi, h16x4 &lo) {
-    const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(v01[0], v01[1]), b = __builtin_amdgcn_cvt_pkrtz(v23[0], v23[1]);
-    // (v - hi) 2^11 as fma(hi, -2^11, v 2^11): exact steps, the bits of the subtraction form; the fp16 -> fp32 conversion
-    // of hi rides inside v_fma_mix_f32 (one packed multiply + two mixed fmas per pair instead of two conversions + two packed ops)
-    const f32x2 s01 = v01 * pk1(FFW_SCALE), s23 = v23 * pk1(FFW_SCALE);
-    const fp16x2 c = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)a[0], -FFW_SCALE, s01[0]), __builtin_fmaf((float)a[1], -FFW_SCALE, s01[1])),
-                 d = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)b[0], -FFW_SCALE, s23[0]), __builtin_fmaf((float)b[1], -FFW_SCALE, s23[1]));
-    hi = h16x4{(_Float16)a[0], (_Float16)a[1], (_Float16)b[0], (_Float16)b[1]};
-    lo = h16x4{(_Float16)c[0], (_Float16)c[1], (_Float16)d[0], (_Float16)d[1]};
-}
-__device__ __forceinline__ void ffw_split4(const float v0, const float v1, const float v2, const float v3, h16x4 &hi, h16x4 &lo) {
-    ffw_split4(pk2(v0, v1), pk2(v2, v3), hi, lo);
-}
-__device__ __forceinline__ h16x8 ffw_cat(const h16x4 a, const h16x4 b) {
-    return h16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
-}
 __device__ __forceinline__ void ffw_split8(const float *p0, const float *p1, h16x8 &hi, h16x8 &lo) {
     const float4 v0 = *reinterpret_cast<const float4 *>(p0), v1 = *reinterpret_cast<const float4 *>(p1);
-    h16x4 h0, l0, h1, l1;
-    ffw_split4(v0.x, v0.y, v0.z, v0.w, h0, l0);
-    ffw_split4(v1.x, v1.y, v1.z, v1.w, h1, l1);
-    hi = ffw_cat(h0, h1);
-    lo = ffw_cat(l0, l1);
+    split8_rtz(f32x4{v0.x, v0.y, v0.z, v0.w}, f32x4{v1.x, v1.y, v1.z, v1.w}, hi, lo);
 }
 
 template <int L>
@@ -692,7 +663,7 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
         const float rstd_ = rsqrtf(var_ * (1.0f / C) + a.eps);                                              \
         h16x4 hi_, lo_;                                                                                     \
         const float4 lnw = FFW_LNW, lnb = FFW_LNB;                                                          \
-        ffw_split4(d01_ * pk1(rstd_) * pk2(lnw.x, lnw.y) + pk2(lnb.x, lnb.y),                               \
+        split4_rtz(d01_ * pk1(rstd_) * pk2(lnw.x, lnw.y) + pk2(lnb.x, lnb.y),                               \
                    d23_ * pk1(rstd_) * pk2(lnw.z, lnw.w) + pk2(lnb.z, lnb.w), hi_, lo_);                     \
         const int P_ = q >> 3, gq_ = (q >> 1) & 3, j0_ = (q & 1) * 4;                                       \
         h16x4 *dst_ = reinterpret_cast<h16x4 *>(bfrag + (P_ * 2) * 64 + 16 * gq_ + ((r + FFW_ROT(gq_) + P_) & 15)) + (j0_ >> 2); \
@@ -722,14 +693,14 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
         }                                                                                                   \
         FFW_GEMM1_PRODUCTS()                                                                                \
         h16x4 h0_, l0_, h1_, l1_;                                                                           \
-        ffw_split4(FFW_U2(0, 0), FFW_U2(0, 2), h0_, l0_);                                                   \
-        ffw_split4(FFW_U2(1, 0), FFW_U2(1, 2), h1_, l1_);                                                   \
-        ufrag[(wv * 2) * 64 + lane] = ffw_cat(h0_, h1_);                                                    \
-        ufrag[(wv * 2 + 1) * 64 + lane] = ffw_cat(l0_, l1_);                                                \
+        split4_rtz(FFW_U2(0, 0), FFW_U2(0, 2), h0_, l0_);                                                   \
+        split4_rtz(FFW_U2(1, 0), FFW_U2(1, 2), h1_, l1_);                                                   \
+        ufrag[(wv * 2) * 64 + lane] = split_cat(h0_, h1_);                                                    \
+        ufrag[(wv * 2 + 1) * 64 + lane] = split_cat(l0_, l1_);                                                \
     }
-#define FFW_U(T_, i_) fmaxf(__builtin_fmaf(ul_[T_][i_] + uk_[T_][i_], FFW_INV, um_[T_][i_]), 0.f)
+#define FFW_U(T_, i_) fmaxf(__builtin_fmaf(ul_[T_][i_] + uk_[T_][i_], SPLIT_INV, um_[T_][i_]), 0.f)
     // elements i_, i_ + 1 at once: relu(fma(ul + uk, 2^-11, um))
-#define FFW_U2(T_, i_) ffw_relu2(pk_fma(pk2(ul_[T_][i_], ul_[T_][i_ + 1]) + pk2(uk_[T_][i_], uk_[T_][i_ + 1]), pk1(FFW_INV), \
+#define FFW_U2(T_, i_) ffw_relu2(pk_fma(pk2(ul_[T_][i_], ul_[T_][i_ + 1]) + pk2(uk_[T_][i_], uk_[T_][i_ + 1]), pk1(SPLIT_INV), \
                                         pk2(um_[T_][i_], um_[T_][i_ + 1])))
 
     // ---- the first tile's rows are requested before the weights (both pure latency) -------------------------
@@ -856,7 +827,7 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
                         n23_ = d23_ * pk1(rstd_) * pk2(lnw.z, lnw.w) + pk2(lnb.z, lnb.w);
                     } else {
                         h16x4 hi_, lo_;
-                        ffw_split4(n01_, n23_, hi_, lo_);
+                        split4_rtz(n01_, n23_, hi_, lo_);
                         const int P_ = q >> 3, gq_ = (q >> 1) & 3, j0_ = (q & 1) * 4;
                         h16x4 *dst_ = reinterpret_cast<h16x4 *>(bfrag + (P_ * 2) * 64 + 16 * gq_ + ((r + FFW_ROT(gq_) + P_) & 15)) + (j0_ >> 2);
                         dst_[0] = hi_;
@@ -868,8 +839,8 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
                 __builtin_amdgcn_sched_barrier(0);
             }
             {
-                const f32x2 y01 = pk_fma(pk2(l[0], l[1]) + pk2(k[0], k[1]), pk1(FFW_INV), pk2(m[0], m[1])),
-                            y23 = pk_fma(pk2(l[2], l[3]) + pk2(k[2], k[3]), pk1(FFW_INV), pk2(m[2], m[3]));
+                const f32x2 y01 = pk_fma(pk2(l[0], l[1]) + pk2(k[0], k[1]), pk1(SPLIT_INV), pk2(m[0], m[1])),
+                            y23 = pk_fma(pk2(l[2], l[3]) + pk2(k[2], k[3]), pk1(SPLIT_INV), pk2(m[2], m[3]));
                 *reinterpret_cast<float4 *>(ytile + la * PS + 16 * wv + 4 * g) = make_float4(y01[0], y01[1], y23[0], y23[1]);
             }
         }
@@ -928,13 +899,13 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
                         *reinterpret_cast<float4 *>(a.y_norm + row * C + 4 * q) = make_float4(n01[0], n01[1], n23[0], n23[1]);
                     }
                 }
-                if (st == (NP + 1 < NS1 ? NP + 1 : NS1 - 1)) ffw_split4(FFW_U2(0, 0), FFW_U2(0, 2), h0_, l0_);
+                if (st == (NP + 1 < NS1 ? NP + 1 : NS1 - 1)) split4_rtz(FFW_U2(0, 0), FFW_U2(0, 2), h0_, l0_);
                 __builtin_amdgcn_sched_barrier(0);
             }
             (void)NPC1;
-            ffw_split4(FFW_U2(1, 0), FFW_U2(1, 2), h1_, l1_);
-            ufrag[(wv * 2) * 64 + lane] = ffw_cat(h0_, h1_);
-            ufrag[(wv * 2 + 1) * 64 + lane] = ffw_cat(l0_, l1_);
+            split4_rtz(FFW_U2(1, 0), FFW_U2(1, 2), h1_, l1_);
+            ufrag[(wv * 2) * 64 + lane] = split_cat(h0_, h1_);
+            ufrag[(wv * 2 + 1) * 64 + lane] = split_cat(l0_, l1_);
         }
         WSTAMP(4)
         __syncthreads();

@@ -12,9 +12,8 @@
 // by 4 floats) and streams 16-row tiles: a lane loads 16 bytes of its row per 16 columns of K (the next tile's loads in
 // flight under the current tile's products), the B operand is one 16-byte LDS read per four v_mfma_f32_16x16x4_f32 -- A and
 // B agree on which four k a lane pair holds, so no operand is rearranged.
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define LR_WAVES 8
 #define LR_MFMA(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
 

@@ -11,12 +11,10 @@
 // rows per instruction; the tile list of a wave is a runtime table, its accumulators a compile-time array).  A bias
 // gradient rides along as one more column tile against a constant 1.  The slices' partial slabs are then added in slice
 // order by a second launch: no atomics, bit-identical from run to run.
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 #define WG_WAVES 4
 #define WG_ROWS 16  // rows staged per step
-#define MFMA4(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x4f32((av), (bv), acc, 0, 0, 0)
 
 // slab layout: [slice][tile][lane 64][4] floats, tile = to * ntc_ext + tc (tc == ntc: the bias column tile)
 template <int TPW>

@@ -15,20 +15,13 @@
 //             lane, BatchNorm (eval: running statistics) + ReLU, writes x1;
 //   k_pfn_rowmax  the per-voxel max of x1 / x2 (order-preserving integer atomics: order independent, deterministic; one
 //             wavefront per point so that an atomic instruction covers 256 contiguous bytes of one voxel row);
-//   k_pfn2_h  the 128 -> 128 layer on split-fp16 matrix operands (the arithmetic and tile structure of csrc/linear_rows_h.hip:
+//   k_pfn2_h  the 128 -> 128 layer on split-fp16 matrix operands (the arithmetic of csrc/split_f16.hip.h, the tile structure of csrc/linear_rows_h.hip:
 //             the weight matrix as hi / lo MFMA fragments in LDS, 16-point tiles, rows normalised by a power of two): a tile's
 //             rows are gathered as [x1[p] ; m1[voxel[p]]], the epilogue is BatchNorm + ReLU, x2 leaves as 16-byte stores.
 // Five launches (fill, k_pfn1, max, k_pfn2_h, max) instead of ~25.
 // Points outside the grid (voxel < 0) are skipped.  Parity: tests/test_vfe_gpu.py (the reference-run goldens and the numpy
 // restatement at full size, 1e-4 of scale: products re-associated, BatchNorm applied in torch's operation order).
-#include "common.hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-#define PF_SCALE 2048.0f
-#define PF_INV (1.0f / 2048.0f)
-#define PF_MFMA(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
+#include "split_f16.hip.h"
 
 __device__ __forceinline__ void pf_atomic_max(float *addr, float v) {  // (as csrc/vfe.hip: order-preserving integer views)
     if (v >= 0.0f)
@@ -89,18 +82,6 @@ __global__ void __launch_bounds__(256) k_pfn1(Pfn1Args a) {
     *reinterpret_cast<float4 *>(a.x1 + p * 64 + 4 * q) = make_float4(o[0], o[1], o[2], o[3]);
 }
 
-__device__ __forceinline__ void pf_split8(const float4 v0, const float4 v1, float s, h16x8 &hi, h16x8 &lo) {
-    const float x[8] = {v0.x * s, v0.y * s, v0.z * s, v0.w * s, v1.x * s, v1.y * s, v1.z * s, v1.w * s};
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) {
-        const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(x[i], x[i + 1]);
-        const fp16x2 c = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)a[0], -PF_SCALE, x[i] * PF_SCALE),
-                                                    __builtin_fmaf((float)a[1], -PF_SCALE, x[i + 1] * PF_SCALE));
-        hi[i] = (_Float16)a[0]; hi[i + 1] = (_Float16)a[1];
-        lo[i] = (_Float16)c[0]; lo[i + 1] = (_Float16)c[1];
-    }
-}
-
 struct Pfn2Args {
     long long P;
     const int *voxel;
@@ -115,45 +96,16 @@ __global__ void __launch_bounds__(PF2_WAVES *MSSVT_WAVE, 1) k_pfn2_h(Pfn2Args a)
     constexpr int K = 128, N = 128, KS = K / 32, NT = N / 16, IMG = KS * NT * 64;
     extern __shared__ float4 lds4[];
     h16x8 *Bh = reinterpret_cast<h16x8 *>(lds4), *Bl = Bh + IMG;
-    __shared__ float wmax_l[PF2_WAVES];
     __shared__ float4 ep_l[3][N / 4];  // per channel: bias - mean | invstd * weight | bn bias
-    constexpr int FR = IMG / (PF2_WAVES * MSSVT_WAVE);  // 2 fragments per thread
-    float4 wv0[FR], wv1[FR];
-    float wmx = 0.f;
-#pragma unroll
-    for (int i = 0; i < FR; ++i) {
-        const int f = threadIdx.x + i * PF2_WAVES * MSSVT_WAVE;
-        const int ln = f & 63, t = (f >> 6) % NT, P = (f >> 6) / NT;
-        const int n = 16 * t + (ln & 15), k0 = 32 * P + 8 * (ln >> 4);
-        wv0[i] = *reinterpret_cast<const float4 *>(a.W + (size_t)n * K + k0);
-        wv1[i] = *reinterpret_cast<const float4 *>(a.W + (size_t)n * K + k0 + 4);
-        wmx = fmaxf(wmx, fmaxf(fmaxf(fmaxf(fabsf(wv0[i].x), fabsf(wv0[i].y)), fmaxf(fabsf(wv0[i].z), fabsf(wv0[i].w))),
-                               fmaxf(fmaxf(fabsf(wv1[i].x), fabsf(wv1[i].y)), fmaxf(fabsf(wv1[i].z), fabsf(wv1[i].w)))));
-    }
+    WeightImage<K, N, PF2_WAVES> wimg;  // (split_f16.hip.h)
+    const float wmx = wimg.load(a.W);
     if (threadIdx.x < N) {
         const int c = threadIdx.x;
         reinterpret_cast<float *>(ep_l[0])[c] = a.b[c];
         reinterpret_cast<float *>(ep_l[1])[c] = a.bn_mean[c];
         reinterpret_cast<float *>(ep_l[2])[c] = 1.0f / sqrtf(a.bn_var[c] + a.eps);
     }
-    wmx = wave_max(wmx);
-    if (lane_id() == 0) wmax_l[threadIdx.x / MSSVT_WAVE] = wmx;
-    __syncthreads();
-    wmx = 0.f;
-#pragma unroll
-    for (int i = 0; i < PF2_WAVES; ++i) wmx = fmaxf(wmx, wmax_l[i]);
-    const int web = __builtin_bit_cast(int, wmx) & 0x7F800000;
-    const bool wnorm = web != 0 && web < 0x7F000000;
-    const float w_in = wnorm ? __builtin_bit_cast(float, 0x7F000000 - web) : 1.0f;
-    const float w_un = wnorm ? __builtin_bit_cast(float, web) : 1.0f;
-#pragma unroll
-    for (int i = 0; i < FR; ++i) {
-        const int f = threadIdx.x + i * PF2_WAVES * MSSVT_WAVE;
-        h16x8 h, l;
-        pf_split8(wv0[i], wv1[i], w_in, h, l);
-        Bh[f] = h;
-        Bl[f] = l;
-    }
+    const float w_un = wimg.store(wmx, Bh, Bl);
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / MSSVT_WAVE);
     __syncthreads();
@@ -173,35 +125,28 @@ __global__ void __launch_bounds__(PF2_WAVES *MSSVT_WAVE, 1) k_pfn2_h(Pfn2Args a)
         float mx = 0.f;
 #pragma unroll
         for (int P = 0; P < KS; ++P)
-            mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(fabsf(xr[P][0].x), fabsf(xr[P][0].y)), fmaxf(fabsf(xr[P][0].z), fabsf(xr[P][0].w))),
-                                 fmaxf(fmaxf(fabsf(xr[P][1].x), fabsf(xr[P][1].y)), fmaxf(fabsf(xr[P][1].z), fabsf(xr[P][1].w)))));
+            mx = fmaxf(mx, abs_max8(xr[P][0], xr[P][1]));
         mx = fmaxf(mx, lane_xor16(mx));
         mx = fmaxf(mx, lane_xor32(mx));
-        const int eb = __builtin_bit_cast(int, mx) & 0x7F800000;
-        const bool norm = eb != 0 && eb < 0x7F000000;
-        const float s_in = norm ? __builtin_bit_cast(float, 0x7F000000 - eb) : 1.0f;
-        const float un = (norm ? __builtin_bit_cast(float, eb) : 1.0f) * w_un;
+        float s_in, s_un;
+        pow2_norm(mx, s_in, s_un);
+        const float un = s_un * w_un;
         h16x8 ah[KS], al[KS];
 #pragma unroll
-        for (int P = 0; P < KS; ++P) pf_split8(xr[P][0], xr[P][1], s_in, ah[P], al[P]);
+        for (int P = 0; P < KS; ++P) split8_scaled_rtz(xr[P][0], xr[P][1], s_in, ah[P], al[P]);
         float *orow = a.out + (size_t)p * N + 4 * g;  // x2[p]: reduced per voxel by k_pfn_rowmax (256 contiguous bytes per atomic instruction)
 #pragma unroll 2
         for (int t = 0; t < NT; ++t) {
             f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
 #pragma unroll
-            for (int P = 0; P < KS; ++P) {
-                const h16x8 bh = Bh[(P * NT + t) * 64 + lane], bl = Bl[(P * NT + t) * 64 + lane];
-                PF_MFMA(mm, bh, ah[P]);
-                PF_MFMA(cr, bh, al[P]);
-                PF_MFMA(cr, bl, ah[P]);
-            }
+            for (int P = 0; P < KS; ++P) split_product<NT>(mm, cr, Bh, Bl, P, t, lane, ah[P], al[P]);
             // lane (p = la, g) holds x2[p][16 t + 4 g + i]
             const float4 b4 = ep_l[0][4 * t + g], m4 = ep_l[1][4 * t + g], s4 = ep_l[2][4 * t + g];
             const float4 w4 = *reinterpret_cast<const float4 *>(a.bn_w + 16 * t + 4 * g),
                          c4 = *reinterpret_cast<const float4 *>(a.bn_b + 16 * t + 4 * g);
             float r[4];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) r[i] = __builtin_fmaf(cr[i], PF_INV, mm[i]) * un;
+            for (int i = 0; i < 4; ++i) r[i] = __builtin_fmaf(cr[i], SPLIT_INV, mm[i]) * un;
             const float o0 = fmaxf(((r[0] + b4.x) - m4.x) * s4.x * w4.x + c4.x, 0.f), o1 = fmaxf(((r[1] + b4.y) - m4.y) * s4.y * w4.y + c4.y, 0.f),
                         o2 = fmaxf(((r[2] + b4.z) - m4.z) * s4.z * w4.z + c4.z, 0.f), o3 = fmaxf(((r[3] + b4.w) - m4.w) * s4.w * w4.w + c4.w, 0.f);
             if (v >= 0) *reinterpret_cast<float4 *>(orow + 16 * t) = make_float4(o0, o1, o2, o3);

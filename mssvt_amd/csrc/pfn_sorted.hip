@@ -29,14 +29,8 @@
 // The order of the points inside a voxel is the arrival order of the rank atomics (not deterministic); every reduction over
 // a run is order independent (exact integer sums, max), and a row's layer outputs depend on the row alone -- the results are
 // bit-identical run to run (tests/test_vfe_gpu.py asserts it).
-#include "common.hip.h"
+#include "split_f16.hip.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef __fp16 fp16x2 __attribute__((ext_vector_type(2)));
-#define PS_SCALE 2048.0f
-#define PS_INV (1.0f / 2048.0f)
-#define PS_MFMA(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
 #define PS_FIX 1048576.0  // 2^20 steps per metre (csrc/vfe.hip)
 #define PS_SCAN 1024      // counts per scan block
 #define PS_TASK_DEFAULT 16  // sorted rows per task window of k_ps_pfn2 (16 | 32 | 64: 37.3 / 45.9 / 45.1 us at 160k points)
@@ -246,18 +240,6 @@ __global__ void __launch_bounds__(256) k_ps_max1(const float *x1, int N, const i
     *reinterpret_cast<float4 *>(m1 + (size_t)v * 64 + 4 * q) = m;
 }
 
-__device__ __forceinline__ void ps_split8(const float4 v0, const float4 v1, float s, h16x8 &hi, h16x8 &lo) {
-    const float x[8] = {v0.x * s, v0.y * s, v0.z * s, v0.w * s, v1.x * s, v1.y * s, v1.z * s, v1.w * s};
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) {
-        const fp16x2 a = __builtin_amdgcn_cvt_pkrtz(x[i], x[i + 1]);
-        const fp16x2 c = __builtin_amdgcn_cvt_pkrtz(__builtin_fmaf((float)a[0], -PS_SCALE, x[i] * PS_SCALE),
-                                                    __builtin_fmaf((float)a[1], -PS_SCALE, x[i + 1] * PS_SCALE));
-        hi[i] = (_Float16)a[0]; hi[i + 1] = (_Float16)a[1];
-        lo[i] = (_Float16)c[0]; lo[i + 1] = (_Float16)c[1];
-    }
-}
-
 struct Ps2Args {
     int N, task_rows;
     const int *total, *start, *row_voxel;
@@ -274,45 +256,16 @@ __global__ void __launch_bounds__(PS2_WAVES *MSSVT_WAVE, 1) k_ps_pfn2(Ps2Args a)
     extern __shared__ float4 lds4[];
     h16x8 *Bh = reinterpret_cast<h16x8 *>(lds4), *Bl = Bh + IMG;
     float *tiles = reinterpret_cast<float *>(Bl + IMG);
-    __shared__ float wmax_l[PS2_WAVES];
     __shared__ float4 ep_l[3][N / 4];  // per channel: bias | running mean | invstd
-    constexpr int FR = IMG / (PS2_WAVES * MSSVT_WAVE);
-    float4 wv0[FR], wv1[FR];
-    float wmx = 0.f;
-#pragma unroll
-    for (int i = 0; i < FR; ++i) {
-        const int f = threadIdx.x + i * PS2_WAVES * MSSVT_WAVE;
-        const int ln = f & 63, t = (f >> 6) % NT, P = (f >> 6) / NT;
-        const int n = 16 * t + (ln & 15), k0 = 32 * P + 8 * (ln >> 4);
-        wv0[i] = *reinterpret_cast<const float4 *>(a.W + (size_t)n * K + k0);
-        wv1[i] = *reinterpret_cast<const float4 *>(a.W + (size_t)n * K + k0 + 4);
-        wmx = fmaxf(wmx, fmaxf(fmaxf(fmaxf(fabsf(wv0[i].x), fabsf(wv0[i].y)), fmaxf(fabsf(wv0[i].z), fabsf(wv0[i].w))),
-                               fmaxf(fmaxf(fabsf(wv1[i].x), fabsf(wv1[i].y)), fmaxf(fabsf(wv1[i].z), fabsf(wv1[i].w)))));
-    }
+    WeightImage<K, N, PS2_WAVES> wimg;  // (split_f16.hip.h)
+    const float wmx = wimg.load(a.W);
     if (threadIdx.x < N) {
         const int c = threadIdx.x;
         reinterpret_cast<float *>(ep_l[0])[c] = a.b[c];
         reinterpret_cast<float *>(ep_l[1])[c] = a.bn_mean[c];
         reinterpret_cast<float *>(ep_l[2])[c] = 1.0f / sqrtf(a.bn_var[c] + a.eps);
     }
-    wmx = wave_max(wmx);
-    if (lane_id() == 0) wmax_l[threadIdx.x / MSSVT_WAVE] = wmx;
-    __syncthreads();
-    wmx = 0.f;
-#pragma unroll
-    for (int i = 0; i < PS2_WAVES; ++i) wmx = fmaxf(wmx, wmax_l[i]);
-    const int web = __builtin_bit_cast(int, wmx) & 0x7F800000;
-    const bool wnorm = web != 0 && web < 0x7F000000;
-    const float w_in = wnorm ? __builtin_bit_cast(float, 0x7F000000 - web) : 1.0f;
-    const float w_un = wnorm ? __builtin_bit_cast(float, web) : 1.0f;
-#pragma unroll
-    for (int i = 0; i < FR; ++i) {
-        const int f = threadIdx.x + i * PS2_WAVES * MSSVT_WAVE;
-        h16x8 h, l;
-        ps_split8(wv0[i], wv1[i], w_in, h, l);
-        Bh[f] = h;
-        Bl[f] = l;
-    }
+    const float w_un = wimg.store(wmx, Bh, Bl);
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / MSSVT_WAVE);
     float *tile = tiles + wv * 16 * PS2_TS;
@@ -367,17 +320,15 @@ __global__ void __launch_bounds__(PS2_WAVES *MSSVT_WAVE, 1) k_ps_pfn2(Ps2Args a)
             float mx = 0.f;
 #pragma unroll
             for (int P = 0; P < KS; ++P)
-                mx = fmaxf(mx, fmaxf(fmaxf(fmaxf(fabsf(xr[P][0].x), fabsf(xr[P][0].y)), fmaxf(fabsf(xr[P][0].z), fabsf(xr[P][0].w))),
-                                     fmaxf(fmaxf(fabsf(xr[P][1].x), fabsf(xr[P][1].y)), fmaxf(fabsf(xr[P][1].z), fabsf(xr[P][1].w)))));
+                mx = fmaxf(mx, abs_max8(xr[P][0], xr[P][1]));
             mx = fmaxf(mx, lane_xor16(mx));
             mx = fmaxf(mx, lane_xor32(mx));
-            const int eb = __builtin_bit_cast(int, mx) & 0x7F800000;
-            const bool norm = eb != 0 && eb < 0x7F000000;
-            const float s_in = norm ? __builtin_bit_cast(float, 0x7F000000 - eb) : 1.0f;
-            const float un = (norm ? __builtin_bit_cast(float, eb) : 1.0f) * w_un;
+            float s_in, s_un;
+            pow2_norm(mx, s_in, s_un);
+            const float un = s_un * w_un;
             h16x8 ah[KS], al[KS];
 #pragma unroll
-            for (int P = 0; P < KS; ++P) ps_split8(xr[P][0], xr[P][1], s_in, ah[P], al[P]);
+            for (int P = 0; P < KS; ++P) split8_scaled_rtz(xr[P][0], xr[P][1], s_in, ah[P], al[P]);
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -385,19 +336,14 @@ __global__ void __launch_bounds__(PS2_WAVES *MSSVT_WAVE, 1) k_ps_pfn2(Ps2Args a)
                     const int t = h * (NT / 2) + tt;
                     f32x4 mm = f32x4{0.f, 0.f, 0.f, 0.f}, cr = mm;
 #pragma unroll
-                    for (int P = 0; P < KS; ++P) {
-                        const h16x8 bh = Bh[(P * NT + t) * 64 + lane], bl = Bl[(P * NT + t) * 64 + lane];
-                        PS_MFMA(mm, bh, ah[P]);
-                        PS_MFMA(cr, bh, al[P]);
-                        PS_MFMA(cr, bl, ah[P]);
-                    }
+                    for (int P = 0; P < KS; ++P) split_product<NT>(mm, cr, Bh, Bl, P, t, lane, ah[P], al[P]);
                     // lane (row = la, g) holds x2[row][16 t + 4 g + i]
                     const float4 b4 = ep_l[0][4 * t + g], m4 = ep_l[1][4 * t + g], s4 = ep_l[2][4 * t + g];
                     const float4 w4 = *reinterpret_cast<const float4 *>(a.bn_w + 16 * t + 4 * g),
                                  c4 = *reinterpret_cast<const float4 *>(a.bn_b + 16 * t + 4 * g);
                     float r[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) r[i] = __builtin_fmaf(cr[i], PS_INV, mm[i]) * un;
+                    for (int i = 0; i < 4; ++i) r[i] = __builtin_fmaf(cr[i], SPLIT_INV, mm[i]) * un;
                     const float o0 = fmaxf(((r[0] + b4.x) - m4.x) * s4.x * w4.x + c4.x, 0.f), o1 = fmaxf(((r[1] + b4.y) - m4.y) * s4.y * w4.y + c4.y, 0.f),
                                 o2 = fmaxf(((r[2] + b4.z) - m4.z) * s4.z * w4.z + c4.z, 0.f), o3 = fmaxf(((r[3] + b4.w) - m4.w) * s4.w * w4.w + c4.w, 0.f);
                     *reinterpret_cast<float4 *>(tile + la * PS2_TS + 16 * tt + 4 * g) = make_float4(o0, o1, o2, o3);

@@ -1,9 +1,8 @@
 // split_conv.hip.h -- y = act(scale[c] * conv(x, w) + shift[c]) on channels-last fp32 pixels with split-fp16 matrix operands:
 // the one kernel (k_split_conv), exponent-word kernel and weight packer behind bev_conv.hip and head_conv.hip.
-// The library runs these convolutions on the fp32 matrix instruction (1/16 of the 16-bit rate); here every fp32 operand v is
-// carried as hi = fp16(v), lo = fp16((v - hi) 2^11), a product sum = hi hi + 2^-11 (hi lo + lo hi) on v_mfma_f32_16x16x32_f16
-// with fp32 accumulation: the arithmetic of k_linear_rows_h (csrc/linear_rows_h.hip), with both halves rounded to NEAREST here
-// (each operand is then off by at most 2^-23 of itself and the dropped lo lo term is at most 2^-22 of the product).
+// The library runs these convolutions on the fp32 matrix instruction (1/16 of the 16-bit rate); here every operand is split
+// into fp16 halves (the arithmetic of csrc/split_f16.hip.h), both rounded to NEAREST (split8_scaled_rne: each operand is then
+// off by at most 2^-23 of itself and the dropped lo lo term is at most 2^-22 of the product).
 //
 // A convolution over channels-last pixels is one row-GEMM per tap accumulated into one tile: M = output pixels, N = output
 // columns, K = taps x Cin.  Nothing per tap is ever written to global memory: the lanes of a wave read the tap's input pixel
@@ -27,40 +26,17 @@
 // blob: [nsl records of 16 bytes: float w_in (2^-e), float w_un (2^e), int k (columns in use), int kbase (maps before it);
 // zero-padded to 64 bytes][scale nsl NS][shift nsl NS][per slice: its weight blocks].
 #pragma once
-#include "common.hip.h"
-
-typedef float bc_f32x4 __attribute__((ext_vector_type(4)));
-typedef float bc_f32x2 __attribute__((ext_vector_type(2)));
-typedef _Float16 bc_h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 bc_h16x2 __attribute__((ext_vector_type(2)));
+#include "split_f16.hip.h"
 
 #define BC_WAVES 8
 #define BC_WAVE_PIXELS MSSVT_BEV_CONV_WAVE_PIXELS
 #define BC_BLOCK_PIXELS MSSVT_BEV_CONV_BLOCK_PIXELS
 #define BC_THREADS (BC_WAVES * MSSVT_WAVE)
-#define BC_SCALE 2048.0f
-#define BC_INV (1.0f / 2048.0f)
 #define BC_REC_BYTES 16
 #define BC_HDR(NSL) ((((NSL) * BC_REC_BYTES) + 63) / 64 * 64)
-#define BC_MFMA(acc, av, bv) acc = __builtin_amdgcn_mfma_f32_16x16x32_f16((av), (bv), acc, 0, 0, 0)
 static_assert(BC_WAVE_PIXELS == 32 && BC_BLOCK_PIXELS == BC_WAVES * BC_WAVE_PIXELS, "tile constants of the header");
 
 #define BC_KC(CIN) ((CIN) < 128 ? (CIN) : 128)  // input channels per staged weight block
-
-// 8 floats (scaled by the exact power of two s) -> hi and lo halves, both rounded to nearest even
-__device__ __forceinline__ void bc_split8(const float4 v0, const float4 v1, float s, bc_h16x8 &hi, bc_h16x8 &lo) {
-    const float x[8] = {v0.x * s, v0.y * s, v0.z * s, v0.w * s, v1.x * s, v1.y * s, v1.z * s, v1.w * s};
-#pragma unroll
-    for (int i = 0; i < 8; i += 2) {
-        const bc_h16x2 a = __builtin_convertvector((bc_f32x2{x[i], x[i + 1]}), bc_h16x2);
-        // x 2^11 - hi 2^11: exact (the residual of a 24-bit value against its 11-bit rounding has at most 13 bits)
-        const bc_f32x2 r = {__builtin_fmaf((float)a[0], -BC_SCALE, x[i] * BC_SCALE),
-                            __builtin_fmaf((float)a[1], -BC_SCALE, x[i + 1] * BC_SCALE)};
-        const bc_h16x2 c = __builtin_convertvector(r, bc_h16x2);
-        hi[i] = a[0]; hi[i + 1] = a[1];
-        lo[i] = c[0]; lo[i + 1] = c[1];
-    }
-}
 
 // |v| as an integer: ordered like the magnitudes, every NaN above infinity (fmaxf would drop a NaN)
 __device__ __forceinline__ int bc_abs_bits(float v) { return __builtin_bit_cast(int, v) & 0x7FFFFFFF; }
@@ -118,7 +94,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     constexpr int FR = (2 * IMG + BC_THREADS - 1) / BC_THREADS;  // fragments of a block per thread ...
     constexpr int FP = (FR + KS - 1) / KS;  // ... of which a thread moves at most FP under each k step of the previous block
     extern __shared__ float4 bc_lds[];
-    bc_h16x8 *lds = reinterpret_cast<bc_h16x8 *>(bc_lds);  // two buffers of 2 IMG fragments
+    h16x8 *lds = reinterpret_cast<h16x8 *>(bc_lds);  // two buffers of 2 IMG fragments
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / MSSVT_WAVE);
     const int ksize = TAPS ? TAPS : ksize_, stride = TAPS ? 1 : stride_, dil = TAPS ? 1 : dil_;
@@ -130,7 +106,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     const float *rec = reinterpret_cast<const float *>(blob + (SLICED ? (size_t)sl * BC_REC_BYTES : 0));
     const float w_un = rec[1];
     const float *scale = reinterpret_cast<const float *>(blob + hdr) + sl * NS, *shift = scale + cout;
-    const bc_h16x8 *wsrc = reinterpret_cast<const bc_h16x8 *>(blob + hdr + (size_t)cout * 8) + (size_t)sl * nstages * 2 * IMG;
+    const h16x8 *wsrc = reinterpret_cast<const h16x8 *>(blob + hdr + (size_t)cout * 8) + (size_t)sl * nstages * 2 * IMG;
     // block 0 of the weights -> LDS buffer 0
 #pragma unroll
     for (int i = 0; i < FR; ++i) {
@@ -158,16 +134,15 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
                     const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
                     if (iy >= 0 && iy < H && ix >= 0 && ix < W) e = max(e, emap[(size_t)(img[j] + iy * W + ix) * egroups + eoff]);
                 }
-        const int eb = e & 0x7F800000;
-        const bool norm = eb != 0 && eb < 0x7F000000;  // zero / denormal fields and inf / nan fields pass through unscaled
-        s_in[j] = norm ? __builtin_bit_cast(float, 0x7F000000 - eb) : 1.0f;
-        un[j] = (norm ? __builtin_bit_cast(float, eb) : 1.0f) * w_un;
+        float s_un;
+        pow2_norm(__builtin_bit_cast(float, e), s_in[j], s_un);  // (the word's exponent alone counts: a NaN passes through)
+        un[j] = s_un * w_un;
     }
-    bc_f32x4 mm[2][NT], cr[2][NT];
+    f32x4 mm[2][NT], cr[2][NT];
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) mm[j][t] = cr[j][t] = bc_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < NT; ++t) mm[j][t] = cr[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
     // the operand rows of k step (stage, P): 8 floats per tile, zeros where the tap falls outside the image
     float4 xa[2][2];
     auto load_rows = [&](int st, int P) {
@@ -188,11 +163,11 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     __syncthreads();
     for (int st = 0; st < nstages; ++st) {
         const bool more = st + 1 < nstages;
-        const bc_h16x8 *Bh = lds + (st & 1) * 2 * IMG, *Bl = Bh + IMG;
-        bc_h16x8 *dst = lds + ((st + 1) & 1) * 2 * IMG;  // last read during block st - 1: behind the previous barrier
+        const h16x8 *Bh = lds + (st & 1) * 2 * IMG, *Bl = Bh + IMG;
+        h16x8 *dst = lds + ((st + 1) & 1) * 2 * IMG;  // last read during block st - 1: behind the previous barrier
 #pragma unroll
         for (int P = 0; P < KS; ++P) {
-            bc_h16x8 wreg[FP];
+            h16x8 wreg[FP];
             if (more) {  // a piece of the next block's fragments travels under this k step's products
 #pragma unroll
                 for (int i = 0; i < FP; ++i) {
@@ -200,21 +175,21 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
                     if (P * FP + i < FR && f < 2 * IMG) wreg[i] = wsrc[(size_t)(st + 1) * 2 * IMG + f];
                 }
             }
-            bc_h16x8 ah[2], al[2];
+            h16x8 ah[2], al[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) bc_split8(xa[j][0], xa[j][1], s_in[j], ah[j], al[j]);
+            for (int j = 0; j < 2; ++j) split8_scaled_rne(xa[j][0], xa[j][1], s_in[j], ah[j], al[j]);
             if (P + 1 < KS) load_rows(st, P + 1);
             else if (more) load_rows(st + 1, 0);
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const bc_h16x8 bh = Bh[(P * NT + t) * 64 + lane], bl = Bl[(P * NT + t) * 64 + lane];
+                const h16x8 bh = Bh[(P * NT + t) * 64 + lane], bl = Bl[(P * NT + t) * 64 + lane];
                 // Y^T tile: A = the weights' rows n, B = the tile's pixels m
-                BC_MFMA(mm[0][t], bh, ah[0]);
-                BC_MFMA(mm[1][t], bh, ah[1]);
-                BC_MFMA(cr[0][t], bh, al[0]);
-                BC_MFMA(cr[1][t], bh, al[1]);
-                BC_MFMA(cr[0][t], bl, ah[0]);
-                BC_MFMA(cr[1][t], bl, ah[1]);
+                MFMA_H(mm[0][t], bh, ah[0]);
+                MFMA_H(mm[1][t], bh, ah[1]);
+                MFMA_H(cr[0][t], bh, al[0]);
+                MFMA_H(cr[1][t], bh, al[1]);
+                MFMA_H(cr[0][t], bl, ah[0]);
+                MFMA_H(cr[1][t], bl, ah[1]);
             }
             if (more) {
 #pragma unroll
@@ -242,7 +217,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 // (x s_in) (w w_in) / (s_in w_in): both normalisations undone by exact powers of two, then scale / shift
-                const float r = __builtin_fmaf(cr[j][t][i], BC_INV, mm[j][t][i]) * un[j];
+                const float r = __builtin_fmaf(cr[j][t][i], SPLIT_INV, mm[j][t][i]) * un[j];
                 o[i] = __builtin_fmaf(r, sv[i], bv[i]);
                 if (relu) o[i] = o[i] < 0.f ? 0.f : o[i];  // (a NaN stays a NaN: fmaxf would turn it into 0)
                 top = max(top, bc_abs_bits(o[i]));
@@ -297,8 +272,8 @@ static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long
     if (threadIdx.x < (whole ? 16 : 4)) {
         m = 0;
         for (int i = 0; i < 16; ++i) m = max(m, part[i]);
-        const int eb = m & 0x7F800000;
-        const bool norm = eb != 0 && eb < 0x7F000000;
+        int eb;
+        const bool norm = pow2_norm_exponent(m, eb);
         const int word[4] = {norm ? 0x7F000000 - eb : 0x3F800000, norm ? eb : 0x3F800000, whole ? 0 : k, whole ? 0 : kbase};
         reinterpret_cast<int *>(blob + (size_t)sl * BC_REC_BYTES)[threadIdx.x] = threadIdx.x < 4 ? word[threadIdx.x] : 0;
     }
@@ -335,9 +310,9 @@ static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int t
 #pragma unroll
     for (int i = 0; i < 8; ++i)
         v[i] = n >= k ? 0.f : transposed ? w[(size_t)(c0 + i) * k + n] : w[((size_t)n * cin + c0 + i) * ntaps + tap];
-    bc_h16x8 h, l;
-    bc_split8(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), w_in, h, l);
-    bc_h16x8 *blk = reinterpret_cast<bc_h16x8 *>(blob + BC_HDR(nsl) + (size_t)nsl * ns * 8) +
+    h16x8 h, l;
+    split8_scaled_rne(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), w_in, h, l);
+    h16x8 *blk = reinterpret_cast<h16x8 *>(blob + BC_HDR(nsl) + (size_t)nsl * ns * 8) +
                     ((size_t)(sl + slice) * nstages + st) * 2 * IMG;
     blk[f] = h;
     blk[IMG + f] = l;
