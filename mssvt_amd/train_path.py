@@ -101,7 +101,9 @@ class Segments(object):
                           p_idx=torch.arange(M2, dtype=torch.int32, device=dev), n_chunks=M2)
 
     def sum(self, src):
-        if self.idx is None or self.idx.numel() == 0:  # an empty index set: nothing to add (the C entry rejects a NULL idx)
+        # an empty index set, or no source rows (the inverse of a _gather_unique of zero entries keeps one index per
+        # destination, every range empty): nothing to add (the C entry rejects a NULL idx / src)
+        if self.idx is None or self.idx.numel() == 0 or src.shape[0] == 0:
             return torch.zeros((self.n_dst,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
         if self.pending is not None:
             self._cut(int(self.pending.item()))
@@ -118,7 +120,7 @@ def _sum_into(seg, src, dst, c0, accumulate):
     """Segments.sum of `src` (M, cg) written / added to columns [c0, c0 + cg) of `dst` (n_dst, C): no temporary."""
     cg = src.shape[1]
     view = dst[:, c0:c0 + cg]
-    if seg.idx is None or seg.idx.numel() == 0 or seg.n_dst == 0:
+    if seg.idx is None or seg.idx.numel() == 0 or seg.n_dst == 0 or src.shape[0] == 0:
         if not accumulate:
             view.zero_()
         return
