@@ -1086,6 +1086,36 @@ int mssvt_bev_conv_pack(const float *weight, int transposed, const float *bias, 
 int mssvt_bev_conv(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride,
                    int dilation, int relu, int *exp_workspace, float *y, void *stream);
 
+/* The same layers writing a channel slice of a wider tensor, and the 2x2 stride-2 transposed deblock (csrc/bev_conv.hip; ref
+ * pcdet/models/backbones_2d/base_bev_backbone.py:52-63 deblocks, :104-108 the concatenation they replace).  Inference only.
+ * mssvt_bev_conv_into: mssvt_bev_conv with y (B, Ho, Wo, ystride) f32 of which the layer writes channels [ybase, ybase + cout)
+ *   and touches no other; same arithmetic and bits as mssvt_bev_conv.
+ * mssvt_bev_up2_*: ConvTranspose2d(cin, cout, 2, stride 2, no padding) + BatchNorm2d (eval) + ReLU,
+ *   y[b, 2 iy + dy, 2 ix + dx, n] = act(scale[n] * sum_c x[b, iy, ix, c] w[c, n, dy, dx] + shift[n]); (cin, cout) in {(256, 256),
+ *   (64, 32)}.  One launch over the B*H*W input pixels: the four output phases (dy, dx) are four 1x1 layers sharing every input
+ *   row read, same split-fp16 arithmetic (three matrix instructions per product sum, fp32 scale / shift in the epilogue, one
+ *   exact power of two per input pixel and one for the whole weight tensor).
+ * mssvt_bev_up2_pack_bytes: size of the blob (0: not covered): the blob of mssvt_bev_conv_pack for a 1x1 layer of cin inputs and
+ *   4 cout columns -- 64 header bytes, scale (4 cout), shift (4 cout), then per 128-wide (cout = 32: 32-wide) slice of the
+ *   columns and 128-wide chunk of cin the hi and the lo fp16 image; column ph * cout + n holds w[c, n, dy, dx] with
+ *   ph = dy * 2 + dx, scale / shift repeat per phase.
+ * mssvt_bev_up2_pack: weight (cin, cout, 2, 2) as ConvTranspose2d holds it; bias / BatchNorm2d as in mssvt_bev_conv_pack
+ *   (folded in double, rounded once, never into the fp16 weights).  Two launches, no host read.
+ * mssvt_bev_up2: x (B, H, W, cin) f32, y (B, 2H, 2W, ystride) f32 of which channels [ybase, ybase + cout) are written, every
+ *   element of that slice exactly once (no atomics, y is never read) and nothing outside it; exp_workspace (B*H*W) int32,
+ *   written here.  Bit-identical from call to call; scaling x by a power of two scales y bit for bit.
+ * Null / unaligned (16 bytes: x, y, packed) pointers, non-positive sizes, ystride % 4, ybase % 4, ybase < 0 or
+ * ybase + cout > ystride: MSSVT_E_BADARG; an uncovered shape or B*Ho*Wo (the OUTPUT pixels) >= 2^31 - 1024: MSSVT_E_TOOLARGE;
+ * neither launches anything.                                                                                          */
+int mssvt_bev_conv_into(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride,
+                        int dilation, int relu, int *exp_workspace, float *y, int ystride, int ybase, void *stream);
+int mssvt_bev_up2_supported(int cin, int cout);
+long long mssvt_bev_up2_pack_bytes(int cin, int cout);
+int mssvt_bev_up2_pack(const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                       const float *bn_mean, const float *bn_var, float bn_eps, int cin, int cout, void *packed, void *stream);
+int mssvt_bev_up2(const float *x, int B, int H, int W, int cin, const void *packed, int cout, int relu, int *exp_workspace,
+                  float *y, int ystride, int ybase, void *stream);
+
 /* CenterHead's convolutions in eval mode as three launches (csrc/head_conv.hip; ref pcdet/models/dense_heads/center_head.py:
  * shared_conv :76-84, SeparateHead :11-46, forward :350-360), on the kernel of mssvt_bev_conv (csrc/split_conv.hip.h: split-fp16 operands, three
  * matrix instructions per product sum, fp32 scale / shift in the epilogue, exact power-of-two normalisation per output pixel

@@ -9,7 +9,13 @@ convolutions run through the library (MIOpen) -- they are not on the sparse hot 
 ``fused_convs`` (off by default; yaml key ``FUSED_CONVS``): in eval mode with autograd off, an fp32 GPU input and ``AMP`` off,
 the tensors are channels-last and every Conv + BN + ReLU triple that ``bev_conv.routed`` accepts (the 1x1 stride-1 deblock
 included) runs on the split-fp16 kernel of csrc/bev_conv.hip; the 2x2 stride-2 transposed deblock and any other layer run
-through the library on the same tensors.  Shapes and ``data_dict`` keys are unchanged, only strides differ."""
+through the library on the same tensors.  Shapes and ``data_dict`` keys are unchanged, only strides differ.
+
+``fused_deblocks`` (off by default; yaml key ``FUSED_DEBLOCKS``) takes effect only where ``fused_convs`` does and only with it
+on, in a module with one deblock per block and more than one of them: the concatenated ``(B, H, W, sum of upsample filters)``
+tensor is allocated once and every deblock writes its own channel slice of it -- a routed 1x1 stride-1 deblock through
+``bev_conv.conv_bn_act(out=, channel=)``, a 2x2 stride-2 transposed deblock that ``bev_conv.up2_routed`` accepts through
+``bev_conv.up2_bn_act``, any other through the library and a copy into its slice.  There is no ``torch.cat``."""
 import torch
 from torch import nn
 
@@ -53,15 +59,49 @@ class BaseBEVBackbone(nn.Module):
         self.num_bev_features = c_out
         self.use_amp = bool(_get(model_cfg, "AMP", False))
         self.fused_convs = bool(_get(model_cfg, "FUSED_CONVS", False))
+        self.fused_deblocks = bool(_get(model_cfg, "FUSED_DEBLOCKS", False))
+        self._up_filters = [int(c) for c in up_filters[:len(layer_nums)]]
+
+    def _deblock_into(self, bev_conv, deblock, x, out, channel):
+        """`deblock`(x) written into channels [channel, ...) of `out` (None: allocated here from the first result's size)."""
+        layers = list(deblock)
+        conv, bn = layers[0], layers[1] if len(layers) > 1 and isinstance(layers[1], nn.BatchNorm2d) else None
+        relu = len(layers) == 3 and isinstance(layers[2], nn.ReLU)
+        whole = bn is not None and len(layers) == (3 if relu else 2)  # Conv + BN (+ ReLU) and nothing else
+        up2 = whole and bev_conv.up2_routed(conv, bn)
+        if up2 or (whole and bev_conv.routed(conv, bn) and conv.stride[0] == 1):
+            s = 2 if up2 else 1
+            if out is None:
+                out = torch.empty((x.shape[0], s * x.shape[2], s * x.shape[3], sum(self._up_filters)), dtype=torch.float32,
+                                  device=x.device).permute(0, 3, 1, 2)
+            if up2:
+                bev_conv.up2_bn_act(x, bev_conv.pack_up2(conv, bn), relu, out=out, channel=channel)
+            else:
+                bev_conv.conv_bn_act(x, bev_conv.pack(conv, bn), relu, out=out, channel=channel)
+            return out
+        y = bev_conv.run_layers(deblock, x)
+        if out is None:
+            out = torch.empty((y.shape[0], y.shape[2], y.shape[3], sum(self._up_filters)), dtype=torch.float32,
+                              device=y.device).permute(0, 3, 1, 2)
+        out[:, channel:channel + y.shape[1]].copy_(y)
+        return out
 
     def _forward_fused(self, data_dict, feats):
         from . import bev_conv
         x, ups = feats.contiguous(memory_format=torch.channels_last), []
+        into = self.fused_deblocks and len(self.blocks) > 1 and len(self.deblocks) >= len(self.blocks)
+        cat, channel = None, 0  # (into: the concatenated tensor, every deblock writing its own channel slice)
         for i, blk in enumerate(self.blocks):
             x = bev_conv.run_layers(blk, x)
             data_dict["spatial_features_%dx" % int(feats.shape[2] / x.shape[2])] = x
-            ups.append(bev_conv.run_layers(self.deblocks[i], x) if len(self.deblocks) > 0 else x)
-        if len(ups) > 1:
+            if into:
+                cat = self._deblock_into(bev_conv, self.deblocks[i], x, cat, channel)
+                channel += self._up_filters[i]
+            else:
+                ups.append(bev_conv.run_layers(self.deblocks[i], x) if len(self.deblocks) > 0 else x)
+        if into:
+            x = cat
+        elif len(ups) > 1:
             x = torch.cat(ups, dim=1)
         elif len(ups) == 1:
             x = ups[0]

@@ -5,7 +5,10 @@
 //   * the entry points mssvt_bev_conv_supported / _pack_bytes / _pack and mssvt_bev_conv (k_split_expmap over the input, then
 //     k_split_conv with run-time taps: 3x3 at stride 1 / 2 and dilation 1 / 2 with padding = dilation, or 1x1);
 //   * the channel shapes of bc_channels; Cout = 256 is two slices of 128 columns;
-//   * one header record for the whole tensor: ONE power of two for all weights, k and kbase unused (zero).
+//   * one header record for the whole tensor: ONE power of two for all weights, k and kbase unused (zero);
+//   * mssvt_bev_conv_into, the same layers writing a channel slice of a wider tensor (BC_ROWS_INTO), and mssvt_bev_up2_*, the
+//     2 x 2 stride-2 transposed deblock (ref base_bev_backbone.py:52-63) as a 1 x 1 layer of 4 Cout columns (BC_UP2): the blob
+//     is the BEV blob of that layer, column ph Cout + n with ph = dy 2 + dx, scale / shift repeated per phase.
 #include "split_conv.hip.h"
 
 #define BC_NS(COUT) ((COUT) < 128 ? (COUT) : 128)  // output channels per workgroup (slice)
@@ -38,23 +41,78 @@ extern "C" int mssvt_bev_conv_pack(const float *weight, int transposed, const fl
 }
 
 // x (B, H, W, cin) f32, packed = mssvt_bev_conv_pack's blob, exp_workspace (B H W) int32 (written here, no need to clear),
-// y (B, Ho, Wo, cout) f32 with Ho = (H + 2 p - 2 d (k - 1) / 2 - 1) / stride + 1, p = d for 3 x 3 and 0 for 1 x 1
-extern "C" int mssvt_bev_conv(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride,
-                              int dilation, int relu, int *exp_workspace, float *y, void *stream) {
+// y (B, Ho, Wo, cout) f32 with Ho = (H + 2 p - 2 d (k - 1) / 2 - 1) / stride + 1, p = d for 3 x 3 and 0 for 1 x 1; INTO: y's pixels
+// are rows of ystride floats of which the layer writes channels [ybase, ybase + cout)
+template <bool INTO>
+static int bc_conv(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride, int dilation,
+                   int relu, int *exp_workspace, float *y, int ystride, int ybase, hipStream_t st) {
     if (!x || !packed || !exp_workspace || !y || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || ksize <= 0 ||
         stride <= 0 || dilation <= 0 || bc_misaligned(x) || bc_misaligned(y) || bc_misaligned(packed))
         return MSSVT_E_BADARG;
+    if (INTO && (ystride <= 0 || ybase < 0 || ystride % 4 || ybase % 4 || (long long)ybase + cout > ystride)) return MSSVT_E_BADARG;
     if (!mssvt_bev_conv_supported(ksize, cin, cout, stride, dilation) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
     const int Ho = (H - 1) / stride + 1, Wo = (W - 1) / stride + 1;  // padding = dilation (3 x 3) / 0 (1 x 1)
-    hipStream_t st = (hipStream_t)stream;
-#define BC_GO(CI, NSL)                                                                                                     \
-    if (cin == CI && BC_NS(cout) == NSL) {                                                                                 \
-        const int status = bc_expmap<CI, CI / 4>(x, (long long)B * H * W, exp_workspace, st);                              \
-        if (status != MSSVT_OK) return status;                                                                             \
-        return bc_launch<CI, NSL, 0, false, BC_ROWS>(x, CI, 0, H, W, Ho, Wo, B * Ho * Wo, packed, cout / NSL, ksize, stride, \
-                                                     dilation, exp_workspace, 1, relu, y, nullptr, st);                    \
+#define BC_GO(CI, NSL)                                                                                                      \
+    if (cin == CI && BC_NS(cout) == NSL) {                                                                                  \
+        const int status = bc_expmap<CI, CI / 4>(x, (long long)B * H * W, exp_workspace, st);                               \
+        if (status != MSSVT_OK) return status;                                                                              \
+        return bc_launch<CI, NSL, 0, false, INTO ? BC_ROWS_INTO : BC_ROWS>(x, CI, 0, H, W, Ho, Wo, B * Ho * Wo, packed,      \
+                                                                           cout / NSL, ksize, stride, dilation, exp_workspace, \
+                                                                           1, relu, y, nullptr, ystride, ybase, st);         \
     }
     BC_GO(128, 128) BC_GO(256, 128) BC_GO(32, 32) BC_GO(32, 64) BC_GO(64, 64)
+#undef BC_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+extern "C" int mssvt_bev_conv(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout, int stride,
+                              int dilation, int relu, int *exp_workspace, float *y, void *stream) {
+    return bc_conv<false>(x, B, H, W, cin, packed, ksize, cout, stride, dilation, relu, exp_workspace, y, 0, 0, (hipStream_t)stream);
+}
+
+extern "C" int mssvt_bev_conv_into(const float *x, int B, int H, int W, int cin, const void *packed, int ksize, int cout,
+                                   int stride, int dilation, int relu, int *exp_workspace, float *y, int ystride, int ybase,
+                                   void *stream) {
+    return bc_conv<true>(x, B, H, W, cin, packed, ksize, cout, stride, dilation, relu, exp_workspace, y, ystride, ybase,
+                         (hipStream_t)stream);
+}
+
+// ---- up-2: ConvTranspose2d(cin, cout, 2, stride = 2) + BatchNorm2d + ReLU as the 1 x 1 layer of 4 cout columns (BC_UP2) -----
+extern "C" int mssvt_bev_up2_supported(int cin, int cout) { return (cin == 256 && cout == 256) || (cin == 64 && cout == 32) ? 1 : 0; }
+
+extern "C" long long mssvt_bev_up2_pack_bytes(int cin, int cout) {
+    if (!mssvt_bev_up2_supported(cin, cout)) return 0;
+    return BC_HDR(1) + 8ll * 4 * cout + 4ll * cin * 4 * cout;
+}
+
+extern "C" int mssvt_bev_up2_pack(const float *weight, const float *bias, const float *bn_weight, const float *bn_bias,
+                                  const float *bn_mean, const float *bn_var, float bn_eps, int cin, int cout, void *packed,
+                                  void *stream) {
+    if (!weight || !packed || cin <= 0 || cout <= 0 || bc_bad_bn(bn_weight, bn_bias, bn_mean, bn_var, bn_eps) || bc_misaligned(packed))
+        return MSSVT_E_BADARG;
+    if (!mssvt_bev_up2_supported(cin, cout)) return MSSVT_E_TOOLARGE;
+    return bc_pack(weight, 2, bias, bn_weight, bn_bias, bn_mean, bn_var, bn_eps, 1, cin, 4 * cout, 0, BC_NS(cout),
+                   4 * cout / BC_NS(cout), 0, 1, packed, (hipStream_t)stream);
+}
+
+// x (B, H, W, cin) f32, packed = mssvt_bev_up2_pack's blob, exp_workspace (B H W) int32 (written here), y (B, 2 H, 2 W, ystride)
+// f32 of which channels [ybase, ybase + cout) are written
+extern "C" int mssvt_bev_up2(const float *x, int B, int H, int W, int cin, const void *packed, int cout, int relu,
+                             int *exp_workspace, float *y, int ystride, int ybase, void *stream) {
+    if (!x || !packed || !exp_workspace || !y || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || ystride <= 0 || ybase < 0 ||
+        ystride % 4 || ybase % 4 || (long long)ybase + cout > ystride || bc_misaligned(x) || bc_misaligned(y) || bc_misaligned(packed))
+        return MSSVT_E_BADARG;
+    // the OUTPUT pixels, 4 B H W, are what the kernel's addresses count
+    if (!mssvt_bev_up2_supported(cin, cout) || (long long)B * H * W > (0x7FFFFFFFll - 4 * BC_BLOCK_PIXELS) / 4) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+#define BC_GO(CI, CO)                                                                                                         \
+    if (cin == CI && cout == CO) {                                                                                            \
+        const int status = bc_expmap<CI, CI / 4>(x, (long long)B * H * W, exp_workspace, st);                                 \
+        if (status != MSSVT_OK) return status;                                                                                \
+        return bc_launch<CI, BC_NS(CO), 0, false, BC_UP2>(x, CI, 0, H, W, H, W, B * H * W, packed, 4 * CO / BC_NS(CO), 1, 1, 1, \
+                                                          exp_workspace, 1, relu, y, nullptr, ystride, ybase, st);            \
+    }
+    BC_GO(256, 256) BC_GO(64, 32)
 #undef BC_GO
     return MSSVT_E_TOOLARGE;
 }

@@ -95,7 +95,7 @@ template <int CIN, int NS, int OUT>
 static int hc_launch(const float *x, int xstride, int gin, int B, int H, int W, const void *packed, int nsl, const int *emap,
                      int egroups, int relu, float *y, int *eout, void *stream) {
     return bc_launch<CIN, NS, 3, true, OUT>(x, xstride, gin, H, W, H, W, B * H * W, packed, nsl, 3, 1, 1, emap, egroups, relu, y,
-                                            eout, (hipStream_t)stream);
+                                            eout, 0, 0, (hipStream_t)stream);
 }
 
 // x (B, H, W, cin) -> y (B, H, W, s) = relu(scale conv + shift); exp_workspace (B H W) int32 written here (the input's

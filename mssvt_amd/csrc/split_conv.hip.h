@@ -12,7 +12,8 @@
 //   * a wave owns BC_WAVE_PIXELS = 32 consecutive output pixels (two 16-row operand tiles that share every weight fragment
 //     read) and NS <= 128 output columns; all 2 x NS / 16 accumulator tiles (mm: hi hi, cr: the cross terms) stay in
 //     registers over every tap and all of Cin -- one accumulation chain per output element;
-//   * a workgroup is 8 waves = BC_BLOCK_PIXELS = 256 output pixels; blockIdx.y is a SLICE of NS output columns;
+//   * a workgroup is 8 waves = BC_BLOCK_PIXELS = 256 output pixels; blockIdx.y is a SLICE of NS output columns (the up-2
+//     form numbers its workgroups itself: at the OUT enum);
 //   * the weights arrive packed (k_split_pack): per (slice, tap, 128-channel chunk of Cin) one contiguous block holding the hi
 //     and the lo image as ready operand fragments [k step][column tile][lane] x 16 bytes.  A block (<= 64 KiB) is copied into
 //     one of two LDS buffers while the previous one is multiplied: one barrier per block;
@@ -77,8 +78,15 @@ struct bc_geom {
     static constexpr size_t LDS = 2 * (size_t)2 * IMG * 16;  // two buffers of a hi and a lo image
 };
 
-enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR };  // OUT: y (M, nsl NS) rows; rows and eout [pixel][nsl], the largest |y| of the
-                                             // pixel's slice as bits; slice sl's k <= 16 maps planar at float kbase B H W
+enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2 };
+// OUT: y (M, nsl NS) rows; rows and eout [pixel][nsl], the largest |y| of the pixel's slice as bits; slice sl's k <= 16 maps
+// planar at float kbase B H W; rows of `ystride` floats of which the layer owns channels [ybase, ybase + nsl NS) (a slice of a
+// wider tensor; ystride % 4 == ybase % 4 == 0 keeps the stores aligned); UP2: the four phases of a 2 x 2 stride-2 transposed
+// convolution as ONE 1 x 1 launch over the INPUT pixels with nsl = 4 Cout / NS slices -- slice sl = (phase ph = dy 2 + dx,
+// column slice cs) of blob columns ph Cout + n, stored to pixel (b, 2 iy + dy, 2 ix + dx) of a (B, 2 H, 2 W, ystride) tensor at
+// channel ybase + cs NS.  The UP2 grid is one-dimensional: block id = ((pixel block / 8) nsl + sl) 8 + pixel block % 8, so the
+// nsl slices that read one input tile follow each other at a distance of 8 ids (consecutive ids go round the chiplets: the
+// slices of a tile share one L2); pixel blocks are padded to a multiple of 8 and a padding block leaves at once.
 
 // TAPS 0: ksize x ksize taps (3: padding = dil, 1: none) at `stride` / `dil`, output Ho x Wo;  TAPS 3: 3 x 3, stride 1,
 // dilation 1, Ho = H, Wo = W as constants (those five arguments are not read).
@@ -88,7 +96,8 @@ enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR };  // OUT: y (M, nsl NS) rows; rows an
 template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
 __global__ void __launch_bounds__(BC_THREADS, 1)
     k_split_conv(const float *x, int xstride_, int gin, int H, int W, int Ho_, int Wo_, int M, const unsigned char *blob, int nsl,
-                 int ksize_, int stride_, int dil_, const int *emap, int egroups_, int relu, float *y, int *eout) {
+                 int ksize_, int stride_, int dil_, const int *emap, int egroups_, int relu, float *y, int *eout, int ystride,
+                 int ybase) {
     using G = bc_geom<CIN, NS>;
     constexpr int KC = G::KC, KS = G::KS, NT = G::NT, CHUNKS = G::CHUNKS, IMG = G::IMG;
     constexpr int FR = (2 * IMG + BC_THREADS - 1) / BC_THREADS;  // fragments of a block per thread ...
@@ -100,7 +109,10 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     const int ksize = TAPS ? TAPS : ksize_, stride = TAPS ? 1 : stride_, dil = TAPS ? 1 : dil_;
     const int Ho = TAPS ? H : Ho_, Wo = TAPS ? W : Wo_, HWo = Ho * Wo;
     const int nstages = ksize * ksize * CHUNKS, pad = ksize == 3 ? dil : 0;
-    const int sl = blockIdx.y, cout = nsl * NS, hdr = SLICED ? BC_HDR(nsl) : BC_HDR(1);
+    const int pb = OUT == BC_UP2 ? (int)(blockIdx.x / (8 * nsl)) * 8 + (int)(blockIdx.x % 8) : (int)blockIdx.x;  // pixel block
+    const int sl = OUT == BC_UP2 ? (int)(blockIdx.x / 8) % nsl : (int)blockIdx.y;
+    if (OUT == BC_UP2 && pb * BC_BLOCK_PIXELS >= M) return;  // (the whole workgroup, before any barrier)
+    const int cout = nsl * NS, hdr = SLICED ? BC_HDR(nsl) : BC_HDR(1);
     const int xstride = SLICED ? xstride_ : CIN, cbase = SLICED ? sl * gin : 0;
     const int egroups = SLICED ? egroups_ : 1, eoff = egroups > 1 ? sl : 0;
     const float *rec = reinterpret_cast<const float *>(blob + (SLICED ? (size_t)sl * BC_REC_BYTES : 0));
@@ -120,7 +132,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     float s_in[2], un[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int m = blockIdx.x * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la;
+        const int m = pb * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la;
         live[j] = m < M;
         const int mc = live[j] ? m : 0, b = mc / HWo, r = mc - b * HWo, oy = r / Wo;
         oy0[j] = oy * stride - pad;
@@ -206,8 +218,14 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         if (OUT != BC_ROWS_WORDS && !live[j]) continue;  // (with words the whole wave takes part in the exchange below)
-        const int m = blockIdx.x * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la, mc = live[j] ? m : 0;
+        const int m = pb * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la, mc = live[j] ? m : 0;
         int top = 0;  // the largest |y| of the lane's columns, as bits
+        size_t row = 0;  // INTO / UP2: the first float of the lane's pixel and slice in y
+        if (OUT == BC_ROWS_INTO) row = (size_t)mc * ystride + ybase + sl * NS;
+        if (OUT == BC_UP2) {  // (Ho = H, Wo = W: the launch is a 1 x 1 layer over the input pixels)
+            const int nc = nsl / 4, ph = sl / nc, b = mc / HWo, r = mc - b * HWo, iy = r / Wo, ix = r - iy * Wo;
+            row = (((size_t)b * 2 * Ho + 2 * iy + (ph >> 1)) * (2 * Wo) + 2 * ix + (ph & 1)) * ystride + ybase + (sl - ph * nc) * NS;
+        }
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const float4 s4 = *reinterpret_cast<const float4 *>(scale + 16 * t + 4 * g);
@@ -230,6 +248,8 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (4 * g + i < kcols) out[(size_t)(4 * g + i) * HWo] = o[i];
+            } else if (OUT == BC_ROWS_INTO || OUT == BC_UP2) {
+                *reinterpret_cast<float4 *>(y + row + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
             } else {
                 *reinterpret_cast<float4 *>(y + (size_t)mc * cout + sl * NS + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
             }
@@ -244,14 +264,16 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
 
 template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
 static int bc_launch(const float *x, int xstride, int gin, int H, int W, int Ho, int Wo, int M, const void *packed, int nsl,
-                     int ksize, int stride, int dil, const int *emap, int egroups, int relu, float *y, int *eout, hipStream_t st) {
+                     int ksize, int stride, int dil, const int *emap, int egroups, int relu, float *y, int *eout, int ystride, int ybase,
+                     hipStream_t st) {
     const auto kernel = k_split_conv<CIN, NS, TAPS, SLICED, OUT>;
     constexpr size_t LDS = bc_geom<CIN, NS>::LDS;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     if (e != hipSuccess) return (int)e;
-    kernel<<<dim3(divup(M, BC_BLOCK_PIXELS), nsl), BC_THREADS, LDS, st>>>(
-        x, xstride, gin, H, W, Ho, Wo, M, reinterpret_cast<const unsigned char *>(packed), nsl, ksize, stride, dil, emap, egroups,
-        relu, y, eout);
+    const int nblocks = divup(M, BC_BLOCK_PIXELS);
+    const dim3 grid = OUT == BC_UP2 ? dim3((nblocks + 7) / 8 * 8 * nsl) : dim3(nblocks, nsl);
+    kernel<<<grid, BC_THREADS, LDS, st>>>(x, xstride, gin, H, W, Ho, Wo, M, reinterpret_cast<const unsigned char *>(packed), nsl,
+                                          ksize, stride, dil, emap, egroups, relu, y, eout, ystride, ybase);
     return mssvt_launch_status();
 }
 
@@ -262,7 +284,7 @@ static int bc_launch(const float *x, int xstride, int gin, int H, int W, int Ho,
 static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long long count, const float *bias, const float *bn_w,
                                                             const float *bn_b, const float *bn_mean, const float *bn_var,
                                                             float eps, int k, int kbase, int ns, int nsl, int sl, int whole,
-                                                            unsigned char *blob) {
+                                                            int period, int hdr, unsigned char *blob) {
     __shared__ int part[16];
     int m = 0;
     for (long long i = threadIdx.x; i < count; i += blockDim.x) m = max(m, bc_abs_bits(w[i]));
@@ -278,14 +300,16 @@ static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long
         reinterpret_cast<int *>(blob + (size_t)sl * BC_REC_BYTES)[threadIdx.x] = threadIdx.x < 4 ? word[threadIdx.x] : 0;
     }
     const int cols = (whole ? nsl : 1) * ns;
-    float *scale = reinterpret_cast<float *>(blob + BC_HDR(nsl)) + (size_t)sl * ns, *shift = scale + (size_t)nsl * ns;
+    float *scale = reinterpret_cast<float *>(blob + hdr) + (size_t)sl * ns, *shift = scale + (size_t)nsl * ns;
     for (int c = threadIdx.x; c < cols; c += blockDim.x) {
         // BatchNorm2d in eval mode: y = (v + bias - mean) gamma / sqrt(var + eps) + beta, folded in double, rounded once;
-        // a column beyond k (the 16-column tile of a narrower branch) is never stored: scale 1, shift 0
-        double s = 1.0, t = (bias && c < k) ? (double)bias[c] : 0.0;
+        // a column beyond k (the 16-column tile of a narrower branch) is never stored: scale 1, shift 0.  Column c is output
+        // channel c % period (period = k, but k / 4 for the four phases of an up-2 layer)
+        const int ch = c % period;
+        double s = 1.0, t = (bias && c < k) ? (double)bias[ch] : 0.0;
         if (bn_mean && c < k) {
-            s = (bn_w ? (double)bn_w[c] : 1.0) / sqrt((double)bn_var[c] + (double)eps);
-            t = (t - (double)bn_mean[c]) * s + (bn_b ? (double)bn_b[c] : 0.0);
+            s = (bn_w ? (double)bn_w[ch] : 1.0) / sqrt((double)bn_var[ch] + (double)eps);
+            t = (t - (double)bn_mean[ch]) * s + (bn_b ? (double)bn_b[ch] : 0.0);
         }
         scale[c] = (float)s;
         shift[c] = (float)t;
@@ -294,9 +318,10 @@ static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long
 
 // one thread per operand fragment: (slice, stage = (tap, chunk), P, t, lane) -> 8 weights of output channel n = slice ns +
 // 16 t + lane % 16 of the tensor (zeros beyond k), c = chunk KC + 32 P + 8 (lane / 16) .., split into the hi and the lo image
-// of the stage's block.  The tensor is a Conv2d weight (k, cin, ksize, ksize), or (cin, k, 1, 1) if `transposed`
+// of the stage's block.  The tensor is a Conv2d weight (k, cin, ksize, ksize), or a ConvTranspose2d weight: `transposed` 1:
+// (cin, k, 1, 1); 2 (ksize = 1): (cin, k / 4, 2, 2), column n = phase (dy 2 + dx) k / 4 + output channel (the UP2 form)
 static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int transposed, int ksize, int cin, int k, int ns,
-                                                           int nsl, int sl, int n_slices, unsigned char *blob) {
+                                                           int nsl, int sl, int n_slices, int hdr, unsigned char *blob) {
     const int KC = BC_KC(cin), KS = KC / 32, NT = ns / 16, CHUNKS = cin / KC, IMG = KS * NT * 64;
     const int ntaps = ksize * ksize, nstages = ntaps * CHUNKS;
     const long long total = (long long)n_slices * nstages * IMG, id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -309,10 +334,13 @@ static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int t
     float v[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-        v[i] = n >= k ? 0.f : transposed ? w[(size_t)(c0 + i) * k + n] : w[((size_t)n * cin + c0 + i) * ntaps + tap];
+        v[i] = n >= k              ? 0.f
+               : transposed == 2 ? w[((size_t)(c0 + i) * (k / 4) + n % (k / 4)) * 4 + n / (k / 4)]
+               : transposed      ? w[(size_t)(c0 + i) * k + n]
+                                 : w[((size_t)n * cin + c0 + i) * ntaps + tap];
     h16x8 h, l;
     split8_scaled_rne(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), w_in, h, l);
-    h16x8 *blk = reinterpret_cast<h16x8 *>(blob + BC_HDR(nsl) + (size_t)nsl * ns * 8) +
+    h16x8 *blk = reinterpret_cast<h16x8 *>(blob + hdr + (size_t)nsl * ns * 8) +
                     ((size_t)(sl + slice) * nstages + st) * 2 * IMG;
     blk[f] = h;
     blk[IMG + f] = l;
@@ -326,12 +354,13 @@ static int bc_pack(const float *w, int transposed, const float *bias, const floa
                    const float *bn_var, float eps, int ksize, int cin, int k, int kbase, int ns, int nsl, int sl, int whole,
                    void *packed, hipStream_t st) {
     unsigned char *blob = reinterpret_cast<unsigned char *>(packed);
-    const int n_slices = whole ? nsl : 1;
+    // a `whole` blob has ONE record (the kernel reads it with SLICED false: 64 header bytes whatever nsl is)
+    const int n_slices = whole ? nsl : 1, hdr = whole ? BC_HDR(1) : BC_HDR(nsl), period = transposed == 2 ? k / 4 : k;
     k_split_prep<<<1, 1024, 0, st>>>(w, (long long)ksize * ksize * cin * k, bias, bn_w, bn_b, bn_mean, bn_var, eps, k, kbase, ns,
-                                     nsl, sl, whole, blob);
+                                     nsl, sl, whole, period, hdr, blob);
     int status = mssvt_launch_status();
     if (status != MSSVT_OK) return status;
     k_split_pack<<<divup((long long)n_slices * ksize * ksize * cin * ns / 8, 256), 256, 0, st>>>(w, transposed, ksize, cin, k, ns,
-                                                                                                 nsl, sl, n_slices, blob);
+                                                                                                 nsl, sl, n_slices, hdr, blob);
     return mssvt_launch_status();
 }

@@ -121,6 +121,19 @@ def main(out_path):
             xr = torch.randn(2, 23, 29, cin, generator=g).clamp_(min=0).to(DEV).permute(0, 3, 1, 2)
             out["bev_conv_%d_%d_s%d_d%d" % (cin, cout, stride, dil)] = \
                 bev_conv.conv_bn_act(xr, bev_conv.pack(conv.to(DEV), None), True).cpu().numpy()
+    # --- the same file's other output forms, each into a channel slice of a wider tensor: a 1 x 1 layer (rows of another stride)
+    # and the 2 x 2 stride-2 transposed layer at 256 -> 256 (eight slices, one-dimensional grid, phase-strided rows)
+    with torch.no_grad():
+        one = torch.nn.ConvTranspose2d(128, 256, 1, stride=1, bias=False)
+        up = torch.nn.ConvTranspose2d(256, 256, 2, stride=2, bias=False)
+        one.weight.copy_(torch.randn(one.weight.shape, generator=g))
+        up.weight.copy_(torch.randn(up.weight.shape, generator=g))
+        wide = torch.zeros(2, 22, 26, 520, device=DEV).permute(0, 3, 1, 2)
+        x1 = torch.randn(2, 22, 26, 128, generator=g).clamp_(min=0).to(DEV).permute(0, 3, 1, 2)
+        x2 = torch.randn(2, 11, 13, 256, generator=g).clamp_(min=0).to(DEV).permute(0, 3, 1, 2)
+        bev_conv.conv_bn_act(x1, bev_conv.pack(one.to(DEV), None), True, out=wide, channel=4)
+        bev_conv.up2_bn_act(x2, bev_conv.pack_up2(up.to(DEV), None), True, out=wide, channel=260)
+        out["bev_conv_into_128_256_and_up2_256_256"] = wide.cpu().numpy()
     # --- csrc/head_conv.hip: shared layer, trunk and finals at the golden (64 -> 32) and the product (512 -> 64) channel counts:
     # one and four input chunks, one to four column tiles, the planar 16-column tile
     from mssvt_amd import head_conv
