@@ -1116,6 +1116,31 @@ int mssvt_bev_up2_pack(const float *weight, const float *bias, const float *bn_w
 int mssvt_bev_up2(const float *x, int B, int H, int W, int cin, const void *packed, int cout, int relu, int *exp_workspace,
                   float *y, int ystride, int ybase, void *stream);
 
+/* The weight gradient of a 3x3, stride-1 convolution with dilation d in {1, 2} and zero padding d, on channels-last f32
+ * tensors (csrc/bev_conv.hip, kernels in csrc/split_wgrad.hip.h): the training path of the layers above,
+ *   dw[o, c, ky, kx] = sum over (b, y, x) of dy[b, y, x, o] * x[b, y + (ky - 1) d, x + (kx - 1) d, c]   (outside the image: 0),
+ * (cin, cout) in {(128,128), (256,256), (32,32), (64,64)}.  A GEMM whose reduction runs over the B*H*W pixels in memory order,
+ * in split-fp16 arithmetic (hi / lo rounded to nearest, three v_mfma_f32_16x16x32_f16 per product sum, fp32 accumulators in
+ * registers).  The pixels are cut into slices of mssvt_bev_conv_wgrad_slice_pixels(cin, cout) (a function of the channel
+ * shape alone: 4096 / 2048 / 256 / 256 for the shapes above; a slice may span two samples); per (slice, tap) the dy rows are
+ * normalised by one exact power of two and the x rows the tap reads by another, both undone exactly on the partial, so
+ * scaling x or dy by a power of two scales dw bit for bit.  Partials go to slabs of the workspace and a second launch adds
+ * them in slice order: no atomics, bit-identical from call to call and across streams, whatever the workspace held.
+ * mssvt_bev_conv_wgrad_supported: 1 if covered, else 0.
+ * mssvt_bev_conv_wgrad_slice_pixels: the slice length (0: shape not covered).
+ * mssvt_bev_conv_wgrad_workspace_bytes: 2 * roundup(4 B H W, 256) (one exponent word per pixel of x and of dy) +
+ *   slices * 9 * cout * cin * 4 (0: not covered, non-positive sizes or too many pixels).
+ * mssvt_bev_conv_wgrad: x (B, H, W, cin), dy (B, H, W, cout), dw (cout, cin, 3, 3) as Conv2d holds it, workspace of
+ *   mssvt_bev_conv_wgrad_workspace_bytes bytes (written here, no need to clear); all 16-byte aligned.  Four launches, no host
+ *   read, no host synchronisation.  Never reads outside x / dy, writes every element of dw exactly once.
+ * Null / unaligned pointers and non-positive sizes: MSSVT_E_BADARG; an uncovered shape or B*H*W >= 2^31 - 1024:
+ * MSSVT_E_TOOLARGE; neither launches anything.                                                                        */
+int mssvt_bev_conv_wgrad_supported(int ksize, int cin, int cout, int stride, int dilation);
+int mssvt_bev_conv_wgrad_slice_pixels(int cin, int cout);
+long long mssvt_bev_conv_wgrad_workspace_bytes(int B, int H, int W, int ksize, int cin, int cout);
+int mssvt_bev_conv_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, int ksize, int dilation,
+                         float *dw, void *workspace, void *stream);
+
 /* CenterHead's convolutions in eval mode as three launches (csrc/head_conv.hip; ref pcdet/models/dense_heads/center_head.py:
  * shared_conv :76-84, SeparateHead :11-46, forward :350-360), on the kernel of mssvt_bev_conv (csrc/split_conv.hip.h: split-fp16 operands, three
  * matrix instructions per product sum, fp32 scale / shift in the epilogue, exact power-of-two normalisation per output pixel

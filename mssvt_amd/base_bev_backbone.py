@@ -15,7 +15,12 @@ through the library on the same tensors.  Shapes and ``data_dict`` keys are unch
 on, in a module with one deblock per block and more than one of them: the concatenated ``(B, H, W, sum of upsample filters)``
 tensor is allocated once and every deblock writes its own channel slice of it -- a routed 1x1 stride-1 deblock through
 ``bev_conv.conv_bn_act(out=, channel=)``, a 2x2 stride-2 transposed deblock that ``bev_conv.up2_routed`` accepts through
-``bev_conv.up2_bn_act``, any other through the library and a copy into its slice.  There is no ``torch.cat``."""
+``bev_conv.up2_bn_act``, any other through the library and a copy into its slice.  There is no ``torch.cat``.
+
+``fused_train`` (off by default; yaml key ``FUSED_TRAIN``, named like ``DynamicVFE``'s): in training mode with autograd on, an
+fp32 GPU input and ``AMP`` off, blocks and deblocks run channels-last through ``bev_conv_train.run_layers_train``: every
+convolution ``bev_conv_train.train_routed`` accepts (3 x 3, stride 1, cin = cout) on the split-fp16 kernels -- forward, input
+gradient and weight gradient; the stride-2 layer, the deblocks, BatchNorm in training mode and ReLU stay torch modules."""
 import torch
 from torch import nn
 
@@ -60,6 +65,7 @@ class BaseBEVBackbone(nn.Module):
         self.use_amp = bool(_get(model_cfg, "AMP", False))
         self.fused_convs = bool(_get(model_cfg, "FUSED_CONVS", False))
         self.fused_deblocks = bool(_get(model_cfg, "FUSED_DEBLOCKS", False))
+        self.fused_train = bool(_get(model_cfg, "FUSED_TRAIN", False))
         self._up_filters = [int(c) for c in up_filters[:len(layer_nums)]]
 
     def _deblock_into(self, bev_conv, deblock, x, out, channel):
@@ -110,8 +116,28 @@ class BaseBEVBackbone(nn.Module):
         data_dict["spatial_features_2d"] = x
         return data_dict
 
+    def _forward_train(self, data_dict, feats):
+        from .bev_conv_train import run_layers_train
+        x, ups = feats.contiguous(memory_format=torch.channels_last), []
+        for i, blk in enumerate(self.blocks):
+            x = run_layers_train(blk, x)
+            data_dict["spatial_features_%dx" % int(feats.shape[2] / x.shape[2])] = x
+            ups.append(run_layers_train(self.deblocks[i], x) if len(self.deblocks) > 0 else x)
+        if len(ups) > 1:
+            x = torch.cat(ups, dim=1)
+        elif len(ups) == 1:
+            x = ups[0]
+        if len(self.deblocks) > len(self.blocks):
+            x = run_layers_train(self.deblocks[-1], x)
+        data_dict["spatial_features_2d"] = x
+        return data_dict
+
     def forward(self, data_dict):
         feats = data_dict["spatial_features"]
+        if self.fused_train:
+            from . import bev_conv_train
+            if bev_conv_train.switch_applies(self, feats):
+                return self._forward_train(data_dict, feats)
         if self.fused_convs:
             from . import bev_conv
             if bev_conv.switch_applies(self, feats):

@@ -195,6 +195,23 @@ def pack(conv, bn=None, pad=None):
 
 
 @torch.no_grad()
+def pack_weight(w, ksize, cin, cout, stride=1, dilation=1):
+    """A plain weight tensor `w` (cout, cin, ksize, ksize) with no bias and no BatchNorm (scale 1, shift 0) as a ``Packed``
+    layer of that stride / dilation, never cached: the training path (bev_conv_train.py) repacks every step.  No host read."""
+    if not (isinstance(w, torch.Tensor) and w.is_cuda and w.dtype == torch.float32 and tuple(w.shape) == (cout, cin, ksize, ksize)):
+        raise MssvtHipError("bev_conv.pack_weight needs an fp32 GPU tensor of shape (%d, %d, %d, %d)" % (cout, cin, ksize, ksize))
+    nbytes = _lib.lib().mssvt_bev_conv_pack_bytes(ksize, cin, cout)
+    if nbytes <= 0:
+        raise MssvtHipError("bev_conv.pack_weight: shape not covered (%d, %d, %d)" % (ksize, cin, cout))
+    w = w.detach().contiguous()
+    blob = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
+    with torch.cuda.device(w.device):
+        _lib.call("mssvt_bev_conv_pack", _lib.ptr(w), 0, None, None, None, None, None, 0.0, ksize, cin, cout, _lib.ptr(blob),
+                  _lib.stream())
+    return Packed(blob, (ksize, cin, cout, stride, dilation, False))
+
+
+@torch.no_grad()
 def pack_up2(conv, bn=None):
     """The packed blob of a 2 x 2 stride-2 transposed layer: `pack`'s cache and key (rebuilt when a tensor changed)."""
     key = _key(conv, bn, "up2")

@@ -8,8 +8,11 @@
 //   * one header record for the whole tensor: ONE power of two for all weights, k and kbase unused (zero);
 //   * mssvt_bev_conv_into, the same layers writing a channel slice of a wider tensor (BC_ROWS_INTO), and mssvt_bev_up2_*, the
 //     2 x 2 stride-2 transposed deblock (ref base_bev_backbone.py:52-63) as a 1 x 1 layer of 4 Cout columns (BC_UP2): the blob
-//     is the BEV blob of that layer, column ph Cout + n with ph = dy 2 + dx, scale / shift repeated per phase.
+//     is the BEV blob of that layer, column ph Cout + n with ph = dy 2 + dx, scale / shift repeated per phase;
+//   * mssvt_bev_conv_wgrad_*, the weight gradient of the 3 x 3 stride-1 layers with cin = cout for the training path
+//     (split_wgrad.hip.h: a GEMM over pixels in slices, partial slabs in a workspace, added in slice order).
 #include "split_conv.hip.h"
+#include "split_wgrad.hip.h"
 
 #define BC_NS(COUT) ((COUT) < 128 ? (COUT) : 128)  // output channels per workgroup (slice)
 
@@ -114,5 +117,42 @@ extern "C" int mssvt_bev_up2(const float *x, int B, int H, int W, int cin, const
     }
     BC_GO(256, 256) BC_GO(64, 32)
 #undef BC_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// ---- the weight gradient of the 3 x 3 stride-1 layers with cin = cout (the kernels: split_wgrad.hip.h) ----------------------
+extern "C" int mssvt_bev_conv_wgrad_supported(int ksize, int cin, int cout, int stride, int dilation) {
+    return ksize == 3 && stride == 1 && (dilation == 1 || dilation == 2) && bw_channels(cin, cout) ? 1 : 0;
+}
+
+extern "C" int mssvt_bev_conv_wgrad_slice_pixels(int cin, int cout) { return bw_channels(cin, cout) ? bw_slice_pixels(cin) : 0; }
+
+// [words of x: B H W int32, padded to 256 bytes][words of dy: the same][slices x 9 slabs of (cout, cin) f32]
+extern "C" long long mssvt_bev_conv_wgrad_workspace_bytes(int B, int H, int W, int ksize, int cin, int cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || !mssvt_bev_conv_wgrad_supported(ksize, cin, cout, 1, 1) || bc_too_many_pixels(B, H, W)) return 0;
+    const long long M = (long long)B * H * W, nslices = (M + bw_slice_pixels(cin) - 1) / bw_slice_pixels(cin);
+    return 2 * bw_round256(4 * M) + nslices * 9 * cin * cout * 4;
+}
+
+extern "C" int mssvt_bev_conv_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, int ksize, int dilation,
+                                    float *dw, void *workspace, void *stream) {
+    if (!x || !dy || !dw || !workspace || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || ksize <= 0 || dilation <= 0 ||
+        bc_misaligned(x) || bc_misaligned(dy) || bc_misaligned(dw) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!mssvt_bev_conv_wgrad_supported(ksize, cin, cout, 1, dilation) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W;
+    int *ex = reinterpret_cast<int *>(workspace), *edy = ex + bw_round256(4 * M) / 4;
+    float *slab = reinterpret_cast<float *>(edy + bw_round256(4 * M) / 4);
+#define BW_GO(CH, TILE)                                                                                           \
+    if (cin == CH) {                                                                                              \
+        int status = bc_expmap<CH, CH / 4>(x, M, ex, st);                                                         \
+        if (status != MSSVT_OK) return status;                                                                    \
+        status = bc_expmap<CH, CH / 4>(dy, M, edy, st);                                                           \
+        if (status != MSSVT_OK) return status;                                                                    \
+        return bw_launch<TILE>(x, dy, H, W, (int)M, cin, cout, dilation, ex, edy, slab, dw, st);                  \
+    }
+    BW_GO(128, 128) BW_GO(256, 128) BW_GO(32, 32) BW_GO(64, 64)
+#undef BW_GO
     return MSSVT_E_TOOLARGE;
 }

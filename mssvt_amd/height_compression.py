@@ -14,6 +14,11 @@ plain library convolutions (MIOpen through torch): they are dense, regular work 
 ``AMP`` off, the grid is gathered channels-last (``mssvt_dense_bev_nhwc``) and every Conv + BN + ReLU triple that
 ``bev_conv.routed`` accepts runs on the split-fp16 kernel of csrc/bev_conv.hip; the other layers run through the library
 on the same channels-last tensors.  The output keeps its logical ``(B, C, H, W)`` shape, only its strides differ.
+
+``fused_train`` (off by default; yaml key ``FUSED_TRAIN``, named like ``DynamicVFE``'s): in training mode with autograd on,
+fp32 features on the GPU and ``AMP`` off, the compress layers run channels-last through ``bev_conv_train.run_layers_train``:
+every convolution ``bev_conv_train.train_routed`` accepts on the split-fp16 kernels (forward, input gradient and weight
+gradient), BatchNorm in training mode, ReLU and any other layer as the torch modules they are.
 """
 import torch
 import torch.nn as nn
@@ -36,6 +41,7 @@ class HeightCompression(nn.Module):
         paddings = _cfg_get(model_cfg, "LAYER_PADDINGS", [1, 1, 2])
         self.use_amp = bool(_cfg_get(model_cfg, "AMP", False))
         self.fused_convs = bool(_cfg_get(model_cfg, "FUSED_CONVS", False))
+        self.fused_train = bool(_cfg_get(model_cfg, "FUSED_TRAIN", False))
         self.compress_layers = None
         if n_layers:
             c = self.num_bev_features
@@ -54,6 +60,15 @@ class HeightCompression(nn.Module):
                 if self.compress_layers is not None:
                     bev = bev_conv.run_layers(self.compress_layers, bev)
                 batch_dict["spatial_features"] = bev
+                batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
+                return batch_dict
+        if self.fused_train and self.compress_layers is not None:
+            from . import bev_conv_train
+            if bev_conv_train.switch_applies(self, sp.features):
+                dense = sp.dense()
+                b, c, d, h, w = dense.shape
+                bev = dense.view(b, c * d, h, w).contiguous(memory_format=torch.channels_last)
+                batch_dict["spatial_features"] = bev_conv_train.run_layers_train(self.compress_layers, bev)
                 batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
                 return batch_dict
         with torch.autocast("cuda", enabled=self.use_amp and sp.features.is_cuda):

@@ -134,6 +134,13 @@ def main(out_path):
         bev_conv.conv_bn_act(x1, bev_conv.pack(one.to(DEV), None), True, out=wide, channel=4)
         bev_conv.up2_bn_act(x2, bev_conv.pack_up2(up.to(DEV), None), True, out=wide, channel=260)
         out["bev_conv_into_128_256_and_up2_256_256"] = wide.cpu().numpy()
+    # --- the same file's weight gradient (split_wgrad.hip.h): the 128-wide tile over two slices, the 256-wide form (four
+    # tiles) and a narrow one
+    from mssvt_amd import bev_conv_train
+    for c, dil, hw in ((128, 2, (70, 73)), (256, 1, (23, 29)), (64, 1, (23, 29))):
+        xr = torch.randn(2, hw[0], hw[1], c, generator=g).to(DEV).permute(0, 3, 1, 2)
+        gr = torch.randn(2, hw[0], hw[1], c, generator=g).to(DEV).permute(0, 3, 1, 2)
+        out["bev_conv_wgrad_%d_d%d" % (c, dil)] = bev_conv_train.conv_wgrad(xr, gr, dil).cpu().numpy()
     # --- csrc/head_conv.hip: shared layer, trunk and finals at the golden (64 -> 32) and the product (512 -> 64) channel counts:
     # one and four input chunks, one to four column tiles, the planar 16-column tile
     from mssvt_amd import head_conv
