@@ -10,7 +10,7 @@
 // fp16 is narrow.  The inference kernels (block_attn.hip, ffn.hip, compress_ws.hip, compress_fused.hip) rely on the caller
 // for the operands' range (fused.py); the training-path kernels (linear_rows_h.hip, pfn_fused.hip, pfn_sorted.hip,
 // split_conv.hip.h) normalise every row / weight matrix by an exact power of two first (pow2_norm) and undo it in the
-// epilogue, so the halves always see values in (-2, 2).
+// epilogue, so the halves always see values in (-2, 2) -- (-4, 4) for a maximum in [2^127, FLT_MAX].
 #pragma once
 #include "common.hip.h"
 
@@ -102,11 +102,15 @@ __device__ __forceinline__ bool pow2_norm_exponent(int max_abs_bits, int &eb) {
     eb = max_abs_bits & 0x7F800000;
     return eb != 0 && eb < 0x7F000000;
 }
+// pow2_norm covers E = 254 (maxima in [2^127, FLT_MAX]) too: 2^(127 - 254) is no normal float, so that row takes 2^-126 /
+// 2^126 and lies in [2, 4), still far inside fp16 (unscaled, its halves would saturate at 65504: a finite, wrong sum).
+// For E = 1 .. 253 the words are the ones above, bit for bit.
 __device__ __forceinline__ void pow2_norm(float max_abs, float &s_in, float &un) {
-    int eb;
-    const bool norm = pow2_norm_exponent(__builtin_bit_cast(int, max_abs), eb);
-    s_in = norm ? __builtin_bit_cast(float, 0x7F000000 - eb) : 1.0f;
-    un = norm ? __builtin_bit_cast(float, eb) : 1.0f;
+    const int eb = __builtin_bit_cast(int, max_abs) & 0x7F800000;
+    const bool norm = eb != 0 && eb <= 0x7F000000;
+    const int sb = max(0x7F000000 - eb, 0x00800000);
+    s_in = norm ? __builtin_bit_cast(float, sb) : 1.0f;
+    un = norm ? __builtin_bit_cast(float, 0x7F000000 - sb) : 1.0f;
 }
 __device__ __forceinline__ float abs_max8(const float4 a, const float4 b) {
     return fmaxf(fmaxf(fmaxf(fabsf(a.x), fabsf(a.y)), fmaxf(fabsf(a.z), fabsf(a.w))),
