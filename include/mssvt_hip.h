@@ -1261,6 +1261,37 @@ int mssvt_vfe_run_max_forward(const float *x, const int *run_off, int num_rows, 
 int mssvt_vfe_run_max_backward(const float *saved, const float *maxima, const float *grad_out, const int *run_off,
                                int num_rows, int num_voxels, int F, int concat, float *parts, float *grad_x, void *stream);
 
+/* BatchNorm2d in TRAINING mode with an optional ReLU behind it (csrc/bn_train.hip; the BatchNorm2d + ReLU pairs of
+ * BaseBEVBackbone and HeightCompression) on dense channels-last fp32
+ * tensors seen as P = B H W rows of C channels, C in {32, 64, 128, 256}.  Three launches each way, no float atomics, no host
+ * read, no host synchronisation; every sum has one fixed order, so results are bit-identical from call to call.
+ * The rows are cut into pieces of mssvt_bn_train_piece_rows(C) = 8192 / C rows (a function of C alone; 0: width not covered);
+ * a workgroup owns mssvt_bn_train_run_pieces(P, C) = ceil(pieces / 1024) consecutive pieces (0: refused).
+ * mssvt_bn_train_workspace_bytes: ((pieces + 2 workgroups) C + 2 C) * 4, or 0 for P < 2, P >= 2^31 or an uncovered width; the
+ *   workspace is written before it is read, its contents on entry do not matter.
+ * mssvt_bn_train_fwd: x, y (P, C); gamma, beta, running_mean, running_var, save_mean, save_invstd (C).  Per channel: mean and
+ *   the biased variance var of the P values (pivot-shifted sums per piece, merged in piece order per workgroup and then in
+ *   workgroup order), save_mean = mean,
+ *   save_invstd = 1 / sqrt(var + eps) (IEEE division and square root), running_mean = (1 - momentum) running_mean +
+ *   momentum mean, running_var = (1 - momentum) running_var + momentum var P / (P - 1), both in place;
+ *   y = (x - mean) save_invstd gamma + beta, max(., 0) behind it if relu != 0 (a NaN stays a NaN).
+ * mssvt_bn_train_bwd: dy, dx (P, C); dgamma, dbeta (C).  g = dy where relu == 0 or the forward's pre-activation, recomputed
+ *   from x bit for bit, is > 0, else 0 (y is not read); dbeta = sum g, dgamma = sum g xhat, xhat = (x - mean) save_invstd,
+ *   dx = gamma save_invstd (g - dbeta / P - xhat dgamma / P).  Linear in dy: scaling dy by a power of two scales all three
+ *   bit for bit.
+ * Null / unaligned (16 bytes) pointers, P < 2, C < 1: MSSVT_E_BADARG; an uncovered width or P >= 2^31: MSSVT_E_TOOLARGE;
+ * neither launches anything.                                                                                           */
+int mssvt_bn_train_supported(int C);
+int mssvt_bn_train_piece_rows(int C);
+int mssvt_bn_train_run_pieces(long long P, int C);
+long long mssvt_bn_train_workspace_bytes(long long P, int C);
+int mssvt_bn_train_fwd(const float *x, long long P, int C, const float *gamma, const float *beta, float eps, float momentum,
+                       float *running_mean, float *running_var, int relu, float *y, float *save_mean, float *save_invstd,
+                       void *workspace, void *stream);
+int mssvt_bn_train_bwd(const float *x, const float *dy, long long P, int C, const float *gamma, const float *beta,
+                       const float *save_mean, const float *save_invstd, int relu, float *dx, float *dgamma, float *dbeta,
+                       void *workspace, void *stream);
+
 /* ======================================================================== *
  * Part 6 -- timing-only launches (csrc/ceiling.hip; no reference counterpart, nothing reads their output): the byte and
  *           instruction mix of k_ffn_ws / k_attn_kvh on the frame's real tables with every dependency between the

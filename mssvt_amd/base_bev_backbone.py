@@ -20,7 +20,11 @@ tensor is allocated once and every deblock writes its own channel slice of it --
 ``fused_train`` (off by default; yaml key ``FUSED_TRAIN``, named like ``DynamicVFE``'s): in training mode with autograd on, an
 fp32 GPU input and ``AMP`` off, blocks and deblocks run channels-last through ``bev_conv_train.run_layers_train``: every
 convolution ``bev_conv_train.train_routed`` accepts (3 x 3, stride 1, cin = cout) on the split-fp16 kernels -- forward, input
-gradient and weight gradient; the stride-2 layer, the deblocks, BatchNorm in training mode and ReLU stay torch modules."""
+gradient and weight gradient; the stride-2 layer, the deblocks, BatchNorm in training mode and ReLU stay torch modules.
+
+``fused_bn`` (off by default; yaml key ``FUSED_BN``) takes effect only where and when ``fused_train`` does: every BatchNorm2d
+that ``bn_train.bn_routed`` accepts then runs, together with the ReLU behind it, through ``bn_train.BnReluFunction`` -- the
+kernels of csrc/bn_train.hip, forward and backward, bit-identical from step to step -- instead of as torch modules."""
 import torch
 from torch import nn
 
@@ -66,6 +70,7 @@ class BaseBEVBackbone(nn.Module):
         self.fused_convs = bool(_get(model_cfg, "FUSED_CONVS", False))
         self.fused_deblocks = bool(_get(model_cfg, "FUSED_DEBLOCKS", False))
         self.fused_train = bool(_get(model_cfg, "FUSED_TRAIN", False))
+        self.fused_bn = bool(_get(model_cfg, "FUSED_BN", False))
         self._up_filters = [int(c) for c in up_filters[:len(layer_nums)]]
 
     def _deblock_into(self, bev_conv, deblock, x, out, channel):
@@ -120,15 +125,15 @@ class BaseBEVBackbone(nn.Module):
         from .bev_conv_train import run_layers_train
         x, ups = feats.contiguous(memory_format=torch.channels_last), []
         for i, blk in enumerate(self.blocks):
-            x = run_layers_train(blk, x)
+            x = run_layers_train(blk, x, fused_bn=self.fused_bn)
             data_dict["spatial_features_%dx" % int(feats.shape[2] / x.shape[2])] = x
-            ups.append(run_layers_train(self.deblocks[i], x) if len(self.deblocks) > 0 else x)
+            ups.append(run_layers_train(self.deblocks[i], x, fused_bn=self.fused_bn) if len(self.deblocks) > 0 else x)
         if len(ups) > 1:
             x = torch.cat(ups, dim=1)
         elif len(ups) == 1:
             x = ups[0]
         if len(self.deblocks) > len(self.blocks):
-            x = run_layers_train(self.deblocks[-1], x)
+            x = run_layers_train(self.deblocks[-1], x, fused_bn=self.fused_bn)
         data_dict["spatial_features_2d"] = x
         return data_dict
 

@@ -9,9 +9,11 @@ channels-last fp32 GPU tensors with a hand-written backward:
     dW        ``conv_wgrad``: mssvt_bev_conv_wgrad, a GEMM over pixels cut into slices whose partial slabs are added in slice
               order -- no atomics, bit-identical from step to step.
 
-The weights are repacked on every call (they change every step).  BatchNorm in training mode, ReLU and every layer the kernel
-does not cover (the stride-2 layer, the 1 x 1 deblock, the transposed deblock) stay torch modules: ``run_layers_train`` runs a
-stack on channels-last tensors and sends only ``train_routed`` convolutions through the Function.
+The weights are repacked on every call (they change every step).  Every layer the kernel does not cover (the stride-2 layer,
+the 1 x 1 deblock, the transposed deblock) stays a torch module: ``run_layers_train`` runs a stack on channels-last tensors and
+sends the ``train_routed`` convolutions through the Function.  BatchNorm in training mode and ReLU stay torch modules too
+unless the modules' second switch, ``fused_bn``, is on: then ``run_layers_train(..., fused_bn=True)`` sends every BatchNorm2d
+that ``bn_train.bn_routed`` accepts, with the ReLU behind it, through ``bn_train.BnReluFunction`` (csrc/bn_train.hip).
 
 ``ROUTED_TRAIN`` lists the product layer shapes the modules send here when their ``fused_train`` switch is on: exactly those
 whose slowest forward + backward beat the library's fastest at B = 1 and B = 4 in tools/time_bev_conv_train.py
@@ -129,15 +131,23 @@ def conv3x3(conv, x):
     return Conv3x3Function.apply(x, conv.weight, bev_conv._pair(conv.dilation)[0])
 
 
-def run_layers_train(layers, x):
+def run_layers_train(layers, x, fused_bn=False):
     """A Conv / BatchNorm / ReLU stack (`layers`: the modules in order) on a channels-last tensor with autograd on: every
     routed convolution through ``Conv3x3Function``, every other module (BatchNorm2d / SyncBatchNorm in training mode and ReLU
-    included) as the torch module it is, on the same channels-last tensors."""
+    included) as the torch module it is, on the same channels-last tensors.  With `fused_bn`, a BatchNorm2d that
+    ``bn_train.bn_routed`` accepts runs through ``bn_train.bn_relu`` together with the ``nn.ReLU`` behind it (in place or not;
+    without one: ``relu=False``); every other BatchNorm and ReLU stays a module."""
     layers = list(layers)
     i, n = 0, len(layers)
+    if fused_bn:
+        from . import bn_train
     while i < n:
         m = layers[i]
-        if isinstance(m, nn.ZeroPad2d) and tuple(m.padding) == (1, 1, 1, 1) and i + 1 < n \
+        if fused_bn and bn_train.bn_routed(m):
+            relu = i + 1 < n and type(layers[i + 1]) is nn.ReLU
+            x = bn_train.bn_relu(m, x, relu)
+            i += 2 if relu else 1
+        elif isinstance(m, nn.ZeroPad2d) and tuple(m.padding) == (1, 1, 1, 1) and i + 1 < n \
                 and isinstance(layers[i + 1], nn.Conv2d) and bev_conv._pair(layers[i + 1].padding) == (0, 0) \
                 and train_routed(layers[i + 1], 1):
             x = conv3x3(layers[i + 1], x)

@@ -19,6 +19,10 @@ on the same channels-last tensors.  The output keeps its logical ``(B, C, H, W)`
 fp32 features on the GPU and ``AMP`` off, the compress layers run channels-last through ``bev_conv_train.run_layers_train``:
 every convolution ``bev_conv_train.train_routed`` accepts on the split-fp16 kernels (forward, input gradient and weight
 gradient), BatchNorm in training mode, ReLU and any other layer as the torch modules they are.
+
+``fused_bn`` (off by default; yaml key ``FUSED_BN``) takes effect only where and when ``fused_train`` does: every BatchNorm2d
+that ``bn_train.bn_routed`` accepts then runs, together with the ReLU behind it, through ``bn_train.BnReluFunction`` (the
+kernels of csrc/bn_train.hip, forward and backward) instead of as torch modules.
 """
 import torch
 import torch.nn as nn
@@ -42,6 +46,7 @@ class HeightCompression(nn.Module):
         self.use_amp = bool(_cfg_get(model_cfg, "AMP", False))
         self.fused_convs = bool(_cfg_get(model_cfg, "FUSED_CONVS", False))
         self.fused_train = bool(_cfg_get(model_cfg, "FUSED_TRAIN", False))
+        self.fused_bn = bool(_cfg_get(model_cfg, "FUSED_BN", False))
         self.compress_layers = None
         if n_layers:
             c = self.num_bev_features
@@ -68,7 +73,7 @@ class HeightCompression(nn.Module):
                 dense = sp.dense()
                 b, c, d, h, w = dense.shape
                 bev = dense.view(b, c * d, h, w).contiguous(memory_format=torch.channels_last)
-                batch_dict["spatial_features"] = bev_conv_train.run_layers_train(self.compress_layers, bev)
+                batch_dict["spatial_features"] = bev_conv_train.run_layers_train(self.compress_layers, bev, fused_bn=self.fused_bn)
                 batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
                 return batch_dict
         with torch.autocast("cuda", enabled=self.use_amp and sp.features.is_cuda):
