@@ -1141,6 +1141,39 @@ long long mssvt_bev_conv_wgrad_workspace_bytes(int B, int H, int W, int ksize, i
 int mssvt_bev_conv_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, int ksize, int dilation,
                          float *dw, void *workspace, void *stream);
 
+/* The backward of a transposed deblock whose kernel equals its stride, ConvTranspose2d(cin, cout, s, stride = s) with s in
+ * {1, 2}, no padding and no bias, on channels-last f32 tensors (csrc/bev_conv.hip, csrc/split_wgrad.hip.h; ref
+ * pcdet/models/backbones_2d/base_bev_backbone.py:52-63).  H, W are the deblock's INPUT grid: x and dx are (B, H, W, cin), dy is
+ * (B, s H, s W, cout), weight and dw are (cin, cout, s, s) as ConvTranspose2d holds them.  (stride, cin, cout) in
+ * {(1,128,256), (2,256,256), (1,32,64), (2,64,32)}.
+ * mssvt_bev_deblock_wgrad:  dw[c, n, dy, dx] = sum over (b, iy, ix) of x[b, iy, ix, c] * dy[b, s iy + dy, s ix + dx, n]:
+ *   mssvt_bev_conv_wgrad's kernel and arithmetic with the phases (dy, dx) as taps, on 128 x 128 (narrow: 32 x 32) tiles of
+ *   (cin, cout).  The B*H*W input pixels are cut into slices of mssvt_bev_deblock_wgrad_slice_pixels (1024 / 2048 / 256 / 256
+ *   for the shapes above; a slice may span two samples); per slice the x rows are normalised by one exact power of two and per
+ *   (slice, phase) the dy rows that phase reads by another, both undone exactly on the partial, so scaling x or dy by a power
+ *   of two scales dw bit for bit.  Partials go to slabs of the workspace and a second launch adds them in slice order: no
+ *   atomics, bit-identical from call to call and across streams, whatever the workspace held.  Four launches, no host read.
+ *   Never reads outside x / dy, writes every element of dw exactly once.
+ * mssvt_bev_deblock_wgrad_workspace_bytes: roundup(4 B H W, 256) + roundup(4 s s B H W, 256) (one exponent word per pixel of x
+ *   and of dy) + slices * s * s * cin * cout * 4 (0: not covered, non-positive sizes or too many pixels).
+ * mssvt_bev_deblock_dgrad:  dx[b, iy, ix, c] = sum over (n, dy, dx) of dy[b, s iy + dy, s ix + dx, n] * weight[c, n, dy, dx]:
+ *   mssvt_bev_conv's kernel over dy with `weight` packed as the Conv2d weight (out = cin, in = cout, ky, kx) it already is --
+ *   s x s taps at stride s, no padding, scale 1, shift 0, no activation; same arithmetic (one exact power of two per dx pixel
+ *   over the dy pixels it reads and one for the weight tensor: scaling dy by a power of two scales dx bit for bit).  The
+ *   packed weights and the exponent words of dy live in the workspace: four launches, no host read.  Never reads outside
+ *   dy / weight, writes every element of dx exactly once, bit-identical from call to call whatever the workspace held.
+ * mssvt_bev_deblock_dgrad_workspace_bytes: roundup(4 s s B H W, 256) + 64 + 8 cin + 4 s s cin cout (0 as above).
+ * All pointers 16-byte aligned; workspaces are written here, no need to clear.  Null / unaligned pointers and non-positive
+ * sizes: MSSVT_E_BADARG; an uncovered shape or s*s*B*H*W >= 2^31 - 1024: MSSVT_E_TOOLARGE; neither launches anything.    */
+int mssvt_bev_deblock_train_supported(int stride, int cin, int cout);
+int mssvt_bev_deblock_wgrad_slice_pixels(int stride, int cin, int cout);
+long long mssvt_bev_deblock_wgrad_workspace_bytes(int B, int H, int W, int stride, int cin, int cout);
+int mssvt_bev_deblock_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, int stride, float *dw,
+                            void *workspace, void *stream);
+long long mssvt_bev_deblock_dgrad_workspace_bytes(int B, int H, int W, int stride, int cin, int cout);
+int mssvt_bev_deblock_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int cout, int stride, float *dx,
+                            void *workspace, void *stream);
+
 /* CenterHead's convolutions in eval mode as three launches (csrc/head_conv.hip; ref pcdet/models/dense_heads/center_head.py:
  * shared_conv :76-84, SeparateHead :11-46, forward :350-360), on the kernel of mssvt_bev_conv (csrc/split_conv.hip.h: split-fp16 operands, three
  * matrix instructions per product sum, fp32 scale / shift in the epilogue, exact power-of-two normalisation per output pixel

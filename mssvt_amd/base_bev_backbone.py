@@ -24,7 +24,13 @@ gradient and weight gradient; the stride-2 layer, the deblocks, BatchNorm in tra
 
 ``fused_bn`` (off by default; yaml key ``FUSED_BN``) takes effect only where and when ``fused_train`` does: every BatchNorm2d
 that ``bn_train.bn_routed`` accepts then runs, together with the ReLU behind it, through ``bn_train.BnReluFunction`` -- the
-kernels of csrc/bn_train.hip, forward and backward, bit-identical from step to step -- instead of as torch modules."""
+kernels of csrc/bn_train.hip, forward and backward, bit-identical from step to step -- instead of as torch modules.
+
+``fused_train_deblocks`` (off by default; yaml key ``FUSED_TRAIN_DEBLOCKS``) takes effect only where and when ``fused_train``
+does, on its own it does nothing: every ``ConvTranspose2d`` deblock that ``bev_deblock_train.deblock_train_routed`` accepts
+(kernel = stride in {1, 2}, no bias, a routed shape) then runs through ``bev_deblock_train.DeblockFunction`` -- forward, input
+gradient and weight gradient on the split-fp16 kernels.  An unrouted deblock, the trailing deblock over the concatenated
+tensor and fractional strides stay modules; BatchNorm + ReLU behind the deblock and ``torch.cat`` stay as they are."""
 import torch
 from torch import nn
 
@@ -71,6 +77,7 @@ class BaseBEVBackbone(nn.Module):
         self.fused_deblocks = bool(_get(model_cfg, "FUSED_DEBLOCKS", False))
         self.fused_train = bool(_get(model_cfg, "FUSED_TRAIN", False))
         self.fused_bn = bool(_get(model_cfg, "FUSED_BN", False))
+        self.fused_train_deblocks = bool(_get(model_cfg, "FUSED_TRAIN_DEBLOCKS", False))
         self._up_filters = [int(c) for c in up_filters[:len(layer_nums)]]
 
     def _deblock_into(self, bev_conv, deblock, x, out, channel):
@@ -127,13 +134,14 @@ class BaseBEVBackbone(nn.Module):
         for i, blk in enumerate(self.blocks):
             x = run_layers_train(blk, x, fused_bn=self.fused_bn)
             data_dict["spatial_features_%dx" % int(feats.shape[2] / x.shape[2])] = x
-            ups.append(run_layers_train(self.deblocks[i], x, fused_bn=self.fused_bn) if len(self.deblocks) > 0 else x)
+            ups.append(run_layers_train(self.deblocks[i], x, fused_bn=self.fused_bn, fused_deblocks=self.fused_train_deblocks)
+                       if len(self.deblocks) > 0 else x)
         if len(ups) > 1:
             x = torch.cat(ups, dim=1)
         elif len(ups) == 1:
             x = ups[0]
         if len(self.deblocks) > len(self.blocks):
-            x = run_layers_train(self.deblocks[-1], x, fused_bn=self.fused_bn)
+            x = run_layers_train(self.deblocks[-1], x, fused_bn=self.fused_bn)  # (the trailing deblock stays a module)
         data_dict["spatial_features_2d"] = x
         return data_dict
 

@@ -11,7 +11,9 @@ channels-last fp32 GPU tensors with a hand-written backward:
 
 The weights are repacked on every call (they change every step).  Every layer the kernel does not cover (the stride-2 layer,
 the 1 x 1 deblock, the transposed deblock) stays a torch module: ``run_layers_train`` runs a stack on channels-last tensors and
-sends the ``train_routed`` convolutions through the Function.  BatchNorm in training mode and ReLU stay torch modules too
+sends the ``train_routed`` convolutions through the Function.  With ``fused_deblocks=True`` the transposed deblocks that
+``bev_deblock_train.deblock_train_routed`` accepts run through ``bev_deblock_train.DeblockFunction`` (the same kernels with
+other tap sets); the stride-2 layer always stays a module.  BatchNorm in training mode and ReLU stay torch modules too
 unless the modules' second switch, ``fused_bn``, is on: then ``run_layers_train(..., fused_bn=True)`` sends every BatchNorm2d
 that ``bn_train.bn_routed`` accepts, with the ReLU behind it, through ``bn_train.BnReluFunction`` (csrc/bn_train.hip).
 
@@ -131,16 +133,20 @@ def conv3x3(conv, x):
     return Conv3x3Function.apply(x, conv.weight, bev_conv._pair(conv.dilation)[0])
 
 
-def run_layers_train(layers, x, fused_bn=False):
+def run_layers_train(layers, x, fused_bn=False, fused_deblocks=False):
     """A Conv / BatchNorm / ReLU stack (`layers`: the modules in order) on a channels-last tensor with autograd on: every
     routed convolution through ``Conv3x3Function``, every other module (BatchNorm2d / SyncBatchNorm in training mode and ReLU
     included) as the torch module it is, on the same channels-last tensors.  With `fused_bn`, a BatchNorm2d that
     ``bn_train.bn_routed`` accepts runs through ``bn_train.bn_relu`` together with the ``nn.ReLU`` behind it (in place or not;
-    without one: ``relu=False``); every other BatchNorm and ReLU stays a module."""
+    without one: ``relu=False``); every other BatchNorm and ReLU stays a module.  With `fused_deblocks`, a ConvTranspose2d that
+    ``bev_deblock_train.deblock_train_routed`` accepts runs through ``bev_deblock_train.DeblockFunction``; every other one
+    stays a module."""
     layers = list(layers)
     i, n = 0, len(layers)
     if fused_bn:
         from . import bn_train
+    if fused_deblocks:
+        from . import bev_deblock_train
     while i < n:
         m = layers[i]
         if fused_bn and bn_train.bn_routed(m):
@@ -154,6 +160,9 @@ def run_layers_train(layers, x, fused_bn=False):
             i += 2
         elif isinstance(m, nn.Conv2d) and train_routed(m):
             x = conv3x3(m, x)
+            i += 1
+        elif fused_deblocks and isinstance(m, nn.ConvTranspose2d) and bev_deblock_train.deblock_train_routed(m):
+            x = bev_deblock_train.deblock(m, x)
             i += 1
         else:
             x = m(x)

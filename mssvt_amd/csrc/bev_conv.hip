@@ -10,7 +10,10 @@
 //     2 x 2 stride-2 transposed deblock (ref base_bev_backbone.py:52-63) as a 1 x 1 layer of 4 Cout columns (BC_UP2): the blob
 //     is the BEV blob of that layer, column ph Cout + n with ph = dy 2 + dx, scale / shift repeated per phase;
 //   * mssvt_bev_conv_wgrad_*, the weight gradient of the 3 x 3 stride-1 layers with cin = cout for the training path
-//     (split_wgrad.hip.h: a GEMM over pixels in slices, partial slabs in a workspace, added in slice order).
+//     (split_wgrad.hip.h: a GEMM over pixels in slices, partial slabs in a workspace, added in slice order);
+//   * mssvt_bev_deblock_*, the backward of the transposed deblocks whose kernel equals their stride s in {1, 2}: the weight
+//     gradient is the same GEMM with the phases (dy, dx) as taps (BW_PHASES), the input gradient is k_split_conv over dY with
+//     the weight tensor (cin, cout, s, s) packed as the Conv2d weight (out, in, ky, kx) it already is: s x s taps at stride s.
 #include "split_conv.hip.h"
 #include "split_wgrad.hip.h"
 
@@ -150,9 +153,89 @@ extern "C" int mssvt_bev_conv_wgrad(const float *x, const float *dy, int B, int 
         if (status != MSSVT_OK) return status;                                                                    \
         status = bc_expmap<CH, CH / 4>(dy, M, edy, st);                                                           \
         if (status != MSSVT_OK) return status;                                                                    \
-        return bw_launch<TILE>(x, dy, H, W, (int)M, cin, cout, dilation, ex, edy, slab, dw, st);                  \
+        return bw_launch<TILE, BW_TAPS3>(x, dy, H, W, (int)M, cin, cout, dilation, 9, bw_slice_pixels(cin), ex, edy, \
+                                         slab, dw, st);                                                           \
     }
     BW_GO(128, 128) BW_GO(256, 128) BW_GO(32, 32) BW_GO(64, 64)
 #undef BW_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// ---- the backward of ConvTranspose2d(cin, cout, s, stride = s), s in {1, 2}: x / dx (B, H, W, cin), dy (B, s H, s W, cout) -------
+extern "C" int mssvt_bev_deblock_train_supported(int stride, int cin, int cout) { return bw_deblock_shape(stride, cin, cout) ? 1 : 0; }
+
+extern "C" int mssvt_bev_deblock_wgrad_slice_pixels(int stride, int cin, int cout) {
+    return bw_deblock_shape(stride, cin, cout) ? bw_deblock_slice_pixels(cin) : 0;
+}
+
+// the kernels' addresses count the s s B H W pixels of dy
+static bool bd_too_many_pixels(int B, int H, int W, int stride) {
+    return (long long)B * H * W > (0x7FFFFFFFll - 4 * BC_BLOCK_PIXELS) / (stride * stride);
+}
+
+// [words of x: B H W int32, padded to 256 bytes][words of dy: s s B H W, padded][slices x s s slabs of (cin, cout) f32]
+extern "C" long long mssvt_bev_deblock_wgrad_workspace_bytes(int B, int H, int W, int stride, int cin, int cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || !bw_deblock_shape(stride, cin, cout) || bd_too_many_pixels(B, H, W, stride)) return 0;
+    const long long M = (long long)B * H * W, slice = bw_deblock_slice_pixels(cin), nslices = (M + slice - 1) / slice;
+    return bw_round256(4 * M) + bw_round256(4 * stride * stride * M) + nslices * stride * stride * cin * cout * 4;
+}
+
+extern "C" int mssvt_bev_deblock_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, int stride, float *dw,
+                                       void *workspace, void *stream) {
+    if (!x || !dy || !dw || !workspace || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || stride <= 0 || bc_misaligned(x) ||
+        bc_misaligned(dy) || bc_misaligned(dw) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!bw_deblock_shape(stride, cin, cout) || bd_too_many_pixels(B, H, W, stride)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W, Mdy = M * stride * stride;
+    int *ex = reinterpret_cast<int *>(workspace), *edy = ex + bw_round256(4 * M) / 4;
+    float *slab = reinterpret_cast<float *>(edy + bw_round256(4 * Mdy) / 4);
+    // bw_launch(tapped, plain, .., cols, rows, ..): rows = cin (x, the plain operand), columns = cout (dy, read at the phase's pixel)
+#define BD_GO(CI, CO, TILE)                                                                                                   \
+    if (cin == CI && cout == CO) {                                                                                            \
+        int status = bc_expmap<CI, CI / 4>(x, M, ex, st);                                                                     \
+        if (status != MSSVT_OK) return status;                                                                                \
+        status = bc_expmap<CO, CO / 4>(dy, Mdy, edy, st);                                                                     \
+        if (status != MSSVT_OK) return status;                                                                                \
+        return bw_launch<TILE, BW_PHASES>(dy, x, H, W, (int)M, cout, cin, stride, stride * stride,                            \
+                                          bw_deblock_slice_pixels(cin), edy, ex, slab, dw, st);                       \
+    }
+    BD_GO(128, 256, 128) BD_GO(256, 256, 128) BD_GO(32, 64, 32) BD_GO(64, 32, 32)
+#undef BD_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// the blob of the Conv2d layer cout -> cin with s x s taps (one header record: 64 bytes, scale, shift, the weight blocks)
+static long long bd_blob_bytes(int stride, int cin, int cout) { return BC_HDR(1) + 8ll * cin + 4ll * stride * stride * cin * cout; }
+
+// [words of dy: s s B H W int32, padded to 256 bytes][the blob]
+extern "C" long long mssvt_bev_deblock_dgrad_workspace_bytes(int B, int H, int W, int stride, int cin, int cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || !bw_deblock_shape(stride, cin, cout) || bd_too_many_pixels(B, H, W, stride)) return 0;
+    return bw_round256(4ll * stride * stride * B * H * W) + bd_blob_bytes(stride, cin, cout);
+}
+
+extern "C" int mssvt_bev_deblock_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int cout, int stride,
+                                       float *dx, void *workspace, void *stream) {
+    if (!dy || !weight || !dx || !workspace || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || stride <= 0 ||
+        bc_misaligned(dy) || bc_misaligned(weight) || bc_misaligned(dx) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!bw_deblock_shape(stride, cin, cout) || bd_too_many_pixels(B, H, W, stride)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const long long Mdy = (long long)B * H * W * stride * stride;
+    int *edy = reinterpret_cast<int *>(workspace);
+    void *blob = edy + bw_round256(4 * Mdy) / 4;
+    // a Conv2d of CO input and CI output channels over dy (B, s H, s W): s x s taps, stride s, no padding, output H x W
+#define BD_GO(CI, CO)                                                                                                         \
+    if (cin == CI && cout == CO) {                                                                                            \
+        int status = bc_pack(weight, 0, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, stride, CO, CI, 0, BC_NS(CI),       \
+                             CI / BC_NS(CI), 0, 1, blob, st);                                                                 \
+        if (status != MSSVT_OK) return status;                                                                                \
+        status = bc_expmap<CO, CO / 4>(dy, Mdy, edy, st);                                                                     \
+        if (status != MSSVT_OK) return status;                                                                                \
+        return bc_launch<CO, BC_NS(CI), 0, false, BC_ROWS>(dy, CO, 0, stride * H, stride * W, H, W, B * H * W, blob,          \
+                                                           CI / BC_NS(CI), stride, stride, 1, edy, 1, 0, dx, nullptr, 0, 0, st); \
+    }
+    BD_GO(128, 256) BD_GO(256, 256) BD_GO(32, 64) BD_GO(64, 32)
+#undef BD_GO
     return MSSVT_E_TOOLARGE;
 }

@@ -20,6 +20,15 @@
 //   * the partial of (slice, tap) is a slab [cout][cin] of the workspace, every element written by exactly one lane;
 //     k_split_wgrad_sum adds the slabs in slice order (fp32, sequential) and writes dW in Conv2d's (cout, cin, 3, 3) layout.
 //     No atomics: bit-identical from call to call, whatever the workspace held.
+//
+// The kernel itself is stated over a PLAIN operand (rows of the tile; read at the reduction pixel m itself) and a TAPPED one
+// (columns; read at the pixel a tap map sends m to), each with its own row pitch, on a rectangular grid of C x C tiles:
+//   BW_TAPS3   the 3 x 3 layer above: plain = dY (rows o), tapped = X at (y + (ky - 1) d, x + (kx - 1) d), 9 taps;
+//   BW_PHASES  the weight gradient of a ConvTranspose2d whose kernel equals its stride s in {1, 2},
+//                  dW[c, n, dy, dx] = sum over (b, iy, ix) of X[b, iy, ix, c] dY[b, s iy + dy, s ix + dx, n]:
+//              plain = X (rows c, the B H W input pixels are the reduction), tapped = dY (columns n) of the (B, s H, s W) grid
+//              at (s iy + dy, s ix + dx), s s taps (the phases; every tapped pixel lies inside).  dW (cin, cout, s, s) is again
+//              [row][column][tap]: the same second launch writes it.
 #pragma once
 #include "split_conv.hip.h"
 
@@ -35,6 +44,12 @@ __device__ __forceinline__ h16x4 bw_read_tr16(const char *p) {
 static bool bw_channels(int cin, int cout) { return cin == cout && (cin == 128 || cin == 256 || cin == 32 || cin == 64); }
 // pixels per slice: of the channel shape alone (the tests sit either side of one, two and three slices)
 static int bw_slice_pixels(int c) { return c >= 256 ? 2048 : c >= 128 ? 4096 : 256; }
+// the same for the transposed deblocks (stride, cin, cout): short slices, the grid at B = 1 has few tiles and phases
+static bool bw_deblock_shape(int stride, int cin, int cout) {
+    return stride == 1 ? (cin == 128 && cout == 256) || (cin == 32 && cout == 64)
+                       : stride == 2 && ((cin == 256 && cout == 256) || (cin == 64 && cout == 32));
+}
+static int bw_deblock_slice_pixels(int cin) { return cin >= 256 ? 2048 : cin >= 128 ? 1024 : 256; }
 static long long bw_round256(long long n) { return (n + 255) / 256 * 256; }
 
 template <int C>
@@ -47,32 +62,39 @@ struct bw_geom {
     static_assert(ITEMS % THREADS == 0 && NT % TM == 0 && NT % TN == 0 && RS % 16 == 0 && WAVES <= 8, "tiling");
 };
 
-// x (B, H, W, cin), dy (B, H, W, cout), ex / edy: their k_split_expmap words; slab [slice][tap][cout][cin].
-// grid (slices, (cout / C) (cin / C), 9)
-template <int C>
+enum { BW_TAPS3, BW_PHASES };
+// tapped_op: the TAPPED operand, pixels of `cols` floats (the tile's columns); plain_op: the PLAIN operand, M = B H W pixels of
+// `rows` floats (the tile's rows); etapped / eplain: their k_split_expmap words; slab [slice][tap][rows][cols].  H, W: the grid
+// of the reduction pixels; step: the dilation (BW_TAPS3) or the stride s (BW_PHASES: tapped_op then has s s M pixels).
+// BW_TAPS3: plain = dY, rows = cout, tapped = X, cols = cin;  BW_PHASES: plain = X, rows = cin, tapped = dY, cols = cout.
+// grid (slices, (rows / C) (cols / C), taps)
+template <int C, int MAP>
 __global__ void __launch_bounds__(bw_geom<C>::THREADS)
-    k_split_wgrad(const float *x, const float *dy, int H, int W, int M, int cin, int cout, int dil, int slice, const int *ex,
-                  const int *edy, float *slab) {
+    k_split_wgrad(const float *tapped_op, const float *plain_op, int H, int W, int M, int cols, int rows, int step, int slice,
+                  const int *etapped, const int *eplain, float *slab) {
     using G = bw_geom<C>;
     constexpr int TM = G::TM, TN = G::TN, RS = G::RS, IMG = G::IMG, BUF = G::BUF, IT = G::IT, THREADS = G::THREADS;
     extern __shared__ __attribute__((aligned(16))) char bw_lds[];
     const int tid = threadIdx.x, lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(tid / MSSVT_WAVE);
-    const int s = blockIdx.x, tiles = cin / C, co0 = ((int)blockIdx.y / tiles) * C, ci0 = ((int)blockIdx.y % tiles) * C;
-    const int tap = blockIdx.z, ky = tap / 3, kx = tap - 3 * ky, oy = (ky - 1) * dil, ox = (kx - 1) * dil;
+    const int s = blockIdx.x, tiles = cols / C, co0 = ((int)blockIdx.y / tiles) * C, ci0 = ((int)blockIdx.y % tiles) * C;
+    const int tap = blockIdx.z, ntaps = gridDim.z, kdim = MAP == BW_TAPS3 ? 3 : step, ky = tap / kdim, kx = tap - kdim * ky;
+    const int oy = MAP == BW_TAPS3 ? (ky - 1) * step : ky, ox = MAP == BW_TAPS3 ? (kx - 1) * step : kx;
     const int HW = H * W;
     const int m0 = s * slice, m1 = M - m0 > slice ? m0 + slice : M;  // the slice's pixels [m0, m1): may span two samples
-    // the pixel the tap reads for output pixel m, or -1 outside the image
+    // the pixel the tap reads for reduction pixel m, or -1 outside the image (a phase never leaves it: s^2 M < 2^31)
     auto tapped = [&](int m) {
-        const int b = m / HW, r = m - b * HW, y = r / W, iy = y + oy, ix = r - y * W + ox;
+        const int b = m / HW, r = m - b * HW, y = r / W;
+        if (MAP == BW_PHASES) return ((b * H + y) * step + oy) * (step * W) + (r - y * W) * step + ox;
+        const int iy = y + oy, ix = r - y * W + ox;
         return (iy >= 0 && iy < H && ix >= 0 && ix < W) ? b * HW + iy * W + ix : -1;
     };
     // ---- the slice's two powers of two
     int edm = 0, exm = 0;
     for (int m = m0 + tid; m < m1; m += THREADS) {
-        edm = max(edm, edy[m]);
+        edm = max(edm, eplain[m]);
         const int q = tapped(m);
-        if (q >= 0) exm = max(exm, ex[q]);
+        if (q >= 0) exm = max(exm, etapped[q]);
     }
 #pragma unroll
     for (int off = 32; off; off >>= 1) {
@@ -104,7 +126,8 @@ __global__ void __launch_bounds__(bw_geom<C>::THREADS)
             dv[i][0] = dv[i][1] = xv[i][0] = xv[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
             const int q = m < m1 ? tapped(m) : -1;
             if (q >= 0) {
-                const float *pd = dy + (size_t)m * cout + co0 + 8 * ch, *pX = x + (size_t)q * cin + ci0 + 8 * ch;
+                const float *pd = plain_op + (size_t)m * rows + co0 + 8 * ch;
+                const float *pX = tapped_op + (size_t)q * cols + ci0 + 8 * ch;
                 dv[i][0] = *reinterpret_cast<const float4 *>(pd);
                 dv[i][1] = *reinterpret_cast<const float4 *>(pd + 4);
                 xv[i][0] = *reinterpret_cast<const float4 *>(pX);
@@ -171,7 +194,7 @@ __global__ void __launch_bounds__(bw_geom<C>::THREADS)
     // they lie on the same side (the intermediate then lies between the sum and the result)
     const bool opposite = (d_un >= 1.f) != (x_un >= 1.f);
     const float un1 = opposite ? d_un * x_un : d_un, un2 = opposite ? 1.f : x_un;
-    float *out = slab + ((size_t)s * 9 + tap) * cout * cin;
+    float *out = slab + ((size_t)s * ntaps + tap) * rows * cols;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -179,31 +202,34 @@ __global__ void __launch_bounds__(bw_geom<C>::THREADS)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int o = co0 + 16 * (TM * wr + i) + 4 * g + r, c = ci0 + 16 * (TN * wc + j) + la;
-                out[(size_t)o * cin + c] = __builtin_fmaf(cr[i][j][r], SPLIT_INV, mm[i][j][r]) * un1 * un2;
+                out[(size_t)o * cols + c] = __builtin_fmaf(cr[i][j][r], SPLIT_INV, mm[i][j][r]) * un1 * un2;
             }
 }
 
-// dw (cout, cin, 3, 3) = the slabs added in slice order; one thread per element, (tap, o, c) with c fastest in the reads
-static __global__ void __launch_bounds__(256) k_split_wgrad_sum(const float *slab, int nslices, int cin, int cout, float *dw) {
-    const int n = 9 * cin * cout, id = blockIdx.x * 256 + threadIdx.x;
+// dw (rows, cols, taps) = the slabs added in slice order; one thread per element, (tap, o, c) with c fastest in the reads
+static __global__ void __launch_bounds__(256) k_split_wgrad_sum(const float *slab, int nslices, int cols, int rows, int ntaps,
+                                                                float *dw) {
+    const int n = ntaps * cols * rows, id = blockIdx.x * 256 + threadIdx.x;
     if (id >= n) return;
-    const int c = id % cin, o = (id / cin) % cout, tap = id / (cin * cout);
+    const int c = id % cols, o = (id / cols) % rows, tap = id / (cols * rows);
     float acc = slab[id];
     for (int s = 1; s < nslices; ++s) acc += slab[(size_t)s * n + id];
-    dw[((size_t)o * cin + c) * 9 + tap] = acc;
+    dw[((size_t)o * cols + c) * ntaps + tap] = acc;
 }
 
-template <int C>
-static int bw_launch(const float *x, const float *dy, int H, int W, int M, int cin, int cout, int dil, const int *ex, const int *edy,
-                     float *slab, float *dw, hipStream_t st) {
+// (the kernel's arguments; dw is (rows, cols, taps))
+template <int C, int MAP>
+static int bw_launch(const float *tapped_op, const float *plain_op, int H, int W, int M, int cols, int rows, int step, int ntaps,
+                     int slice, const int *etapped, const int *eplain, float *slab, float *dw, hipStream_t st) {
     using G = bw_geom<C>;
-    const auto kernel = k_split_wgrad<C>;
+    const auto kernel = k_split_wgrad<C, MAP>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     if (e != hipSuccess) return (int)e;
-    const int slice = bw_slice_pixels(cin), nslices = divup(M, slice), tiles = cin / C;
-    kernel<<<dim3(nslices, tiles * tiles, 9), G::THREADS, G::LDS, st>>>(x, dy, H, W, M, cin, cout, dil, slice, ex, edy, slab);
+    const int nslices = divup(M, slice);
+    kernel<<<dim3(nslices, (rows / C) * (cols / C), ntaps), G::THREADS, G::LDS, st>>>(tapped_op, plain_op, H, W, M, cols, rows, step, slice,
+                                                                                   etapped, eplain, slab);
     int status = mssvt_launch_status();
     if (status != MSSVT_OK) return status;
-    k_split_wgrad_sum<<<divup(9 * cin * cout, 256), 256, 0, st>>>(slab, nslices, cin, cout, dw);
+    k_split_wgrad_sum<<<divup(ntaps * cols * rows, 256), 256, 0, st>>>(slab, nslices, cols, rows, ntaps, dw);
     return mssvt_launch_status();
 }

@@ -141,6 +141,17 @@ def main(out_path):
         xr = torch.randn(2, hw[0], hw[1], c, generator=g).to(DEV).permute(0, 3, 1, 2)
         gr = torch.randn(2, hw[0], hw[1], c, generator=g).to(DEV).permute(0, 3, 1, 2)
         out["bev_conv_wgrad_%d_d%d" % (c, dil)] = bev_conv_train.conv_wgrad(xr, gr, dil).cpu().numpy()
+    # --- the transposed deblocks' backward (bev_deblock_train.py): the weight gradient with the phases as taps at both strides
+    # over more than one slice (1 x 2 and 2 x 2 tiles of 128, and a narrow shape), and the input gradient as a 1 x 1 and a
+    # 2 x 2 stride-2 layer over dY (the 256 -> 256 form: two output slices, two input chunks, four taps)
+    from mssvt_amd import bev_deblock_train
+    for s, cin, cout, hw in ((1, 128, 256, (40, 53)), (2, 256, 256, (46, 47)), (2, 64, 32, (23, 29))):
+        xr = torch.randn(2, hw[0], hw[1], cin, generator=g).to(DEV).permute(0, 3, 1, 2)
+        gr = torch.randn(2, s * hw[0], s * hw[1], cout, generator=g).to(DEV).permute(0, 3, 1, 2)
+        wr = torch.randn(cin, cout, s, s, generator=g).to(DEV)
+        assert 2 * hw[0] * hw[1] > bev_deblock_train.slice_pixels(s, cin, cout)
+        out["bev_deblock_wgrad_s%d_%d_%d" % (s, cin, cout)] = bev_deblock_train.deblock_wgrad(xr, gr, s).cpu().numpy()
+        out["bev_deblock_dgrad_s%d_%d_%d" % (s, cin, cout)] = bev_deblock_train.deblock_dgrad(gr, wr, s).cpu().numpy()
     # --- csrc/head_conv.hip: shared layer, trunk and finals at the golden (64 -> 32) and the product (512 -> 64) channel counts:
     # one and four input chunks, one to four column tiles, the planar 16-column tile
     from mssvt_amd import head_conv
