@@ -23,8 +23,8 @@
 // restatement at full size, 1e-4 of scale: products re-associated, BatchNorm applied in torch's operation order).
 #include "split_f16.hip.h"
 
-__device__ __forceinline__ void pf_atomic_max(float *addr, float v) {  // (as csrc/vfe.hip: order-preserving integer views)
-    if (v >= 0.0f)
+__device__ __forceinline__ void pf_atomic_max(float *addr, float v) {  // (as csrc/vfe.hip: order-preserving integer views, by sign bit)
+    if (__builtin_bit_cast(int, v) >= 0)
         atomicMax(reinterpret_cast<int *>(addr), __builtin_bit_cast(int, v));
     else
         atomicMin(reinterpret_cast<unsigned int *>(addr), __builtin_bit_cast(unsigned int, v));

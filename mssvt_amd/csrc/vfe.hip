@@ -51,10 +51,13 @@ extern "C" int mssvt_voxel_mean_xyz(const float *points, int point_stride, long 
     return mssvt_launch_status();
 }
 
-// float max through integer atomics: non-negative floats order like signed ints, negative floats in
-// reverse like unsigned ints
+// float max through integer atomics: floats with a clear sign bit order like signed ints, floats with the sign bit set in
+// reverse like unsigned ints.  The view is chosen by the SIGN BIT, not by v >= 0: -0.0 (bits INT_MIN) then orders above every
+// negative value and -inf, and below +0.0 (through the signed view it lost to the -inf fill and to every negative float).
+// NaN values are not propagated: a NaN orders by its bits like any other value (above +inf with a clear sign bit, below -inf
+// -- so it never wins -- with the sign bit set).
 __device__ __forceinline__ void atomic_max_float(float *addr, float v) {
-    if (v >= 0.0f)
+    if (__builtin_bit_cast(int, v) >= 0)
         atomicMax(reinterpret_cast<int *>(addr), __builtin_bit_cast(int, v));
     else
         atomicMin(reinterpret_cast<unsigned int *>(addr), __builtin_bit_cast(unsigned int, v));
