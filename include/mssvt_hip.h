@@ -1174,6 +1174,42 @@ long long mssvt_bev_deblock_dgrad_workspace_bytes(int B, int H, int W, int strid
 int mssvt_bev_deblock_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int cout, int stride, float *dx,
                             void *workspace, void *stream);
 
+/* The backward of the 3x3 stride-2 convolution, Conv2d(cin, cout, 3, stride = 2, padding = 1, bias = False) (a ZeroPad2d(1) in
+ * front of padding 0 is the same layer), on channels-last f32 tensors (csrc/bev_conv.hip, csrc/split_wgrad.hip.h,
+ * csrc/split_conv.hip.h; ref pcdet/models/backbones_2d/base_bev_backbone.py:30-38).  H, W are the layer's INPUT grid: x and dx
+ * are (B, H, W, cin), dy is (B, Ho, Wo, cout) with Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1, weight and dw are
+ * (cout, cin, 3, 3) as Conv2d holds them.  (cin, cout) in {(128,256), (32,64)}.  The forward is mssvt_bev_conv at stride 2.
+ * mssvt_bev_down_wgrad:  dw[o, c, ky, kx] = sum over (b, oy, ox) of dy[b, oy, ox, o] * x[b, 2 oy + ky - 1, 2 ox + kx - 1, c]
+ *   (outside the image: 0): mssvt_bev_conv_wgrad's kernel and arithmetic with the stride-2 tap map, on 128 x 128 (narrow:
+ *   32 x 32) tiles of (cout, cin).  The B*Ho*Wo OUTPUT pixels are cut into slices of mssvt_bev_down_wgrad_slice_pixels (2048 /
+ *   256 for the shapes above; a slice may span two samples); per slice the dy rows are normalised by one exact power of two and
+ *   per (slice, tap) the x rows that tap reads by another, both undone exactly on the partial, so scaling x or dy by a power of
+ *   two scales dw bit for bit.  Partials go to slabs of the workspace and a second launch adds them in slice order: no
+ *   atomics, bit-identical from call to call and across streams, whatever the workspace held.  Four launches, no host read.
+ *   Never reads outside x / dy, writes every element of dw exactly once.
+ * mssvt_bev_down_wgrad_workspace_bytes: roundup(4 B H W, 256) + roundup(4 B Ho Wo, 256) (one exponent word per pixel of x and
+ *   of dy) + slices * 9 * cout * cin * 4 (0: not covered, non-positive sizes or too many pixels).
+ * mssvt_bev_down_dgrad:  dx[b, iy, ix, c] = sum over o and the taps (ky, kx) with 2 oy + ky - 1 = iy, 2 ox + kx - 1 = ix of
+ *   dy[b, oy, ox, o] * weight[o, c, ky, kx].  By the parity of (iy, ix) dx falls into four phases, each a dense convolution
+ *   over dy at stride 1: even iy = 2 j takes ky = 1 at oy = j, odd iy = 2 j + 1 takes ky = 2 at oy = j and ky = 0 at oy = j + 1
+ *   (absent when j + 1 = Ho), the same in x -- 1, 2, 2 and 4 taps, the 9 taps of the weight each used once.  One launch of
+ *   mssvt_bev_conv's kernel over dy serves all four (the 4-tap phase first): no zero-stuffed dy, no product with a structural
+ *   zero, no atomics, every element of dx written exactly once; one exact power of two per dx pixel over exactly the dy pixels
+ *   its taps read and one for the weight tensor, so scaling dy or weight by a power of two scales dx bit for bit.  The packed
+ *   weights (the tensor as stored, taps in phase order) and the exponent words of dy live in the workspace: four launches, no
+ *   host read.  Never reads outside dy / weight, bit-identical from call to call whatever the workspace held.
+ * mssvt_bev_down_dgrad_workspace_bytes: roundup(4 B Ho Wo, 256) + 64 + 8 cin + 36 cin cout (0 as above).
+ * All pointers 16-byte aligned; workspaces are written here, no need to clear.  Null / unaligned pointers and non-positive
+ * sizes: MSSVT_E_BADARG; an uncovered shape or B*H*W >= 2^31 - 1024: MSSVT_E_TOOLARGE; neither launches anything.        */
+int mssvt_bev_down_train_supported(int cin, int cout);
+int mssvt_bev_down_wgrad_slice_pixels(int cin, int cout);
+long long mssvt_bev_down_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout);
+int mssvt_bev_down_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, float *dw, void *workspace,
+                         void *stream);
+long long mssvt_bev_down_dgrad_workspace_bytes(int B, int H, int W, int cin, int cout);
+int mssvt_bev_down_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int cout, float *dx, void *workspace,
+                         void *stream);
+
 /* CenterHead's convolutions in eval mode as three launches (csrc/head_conv.hip; ref pcdet/models/dense_heads/center_head.py:
  * shared_conv :76-84, SeparateHead :11-46, forward :350-360), on the kernel of mssvt_bev_conv (csrc/split_conv.hip.h: split-fp16 operands, three
  * matrix instructions per product sum, fp32 scale / shift in the epilogue, exact power-of-two normalisation per output pixel

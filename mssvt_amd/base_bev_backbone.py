@@ -20,7 +20,8 @@ tensor is allocated once and every deblock writes its own channel slice of it --
 ``fused_train`` (off by default; yaml key ``FUSED_TRAIN``, named like ``DynamicVFE``'s): in training mode with autograd on, an
 fp32 GPU input and ``AMP`` off, blocks and deblocks run channels-last through ``bev_conv_train.run_layers_train``: every
 convolution ``bev_conv_train.train_routed`` accepts (3 x 3, stride 1, cin = cout) on the split-fp16 kernels -- forward, input
-gradient and weight gradient; the stride-2 layer, the deblocks, BatchNorm in training mode and ReLU stay torch modules.
+gradient and weight gradient; the stride-2 layer (unless ``fused_train_down``), the deblocks, BatchNorm in training mode and
+ReLU stay torch modules.
 
 ``fused_bn`` (off by default; yaml key ``FUSED_BN``) takes effect only where and when ``fused_train`` does: every BatchNorm2d
 that ``bn_train.bn_routed`` accepts then runs, together with the ReLU behind it, through ``bn_train.BnReluFunction`` -- the
@@ -30,7 +31,13 @@ kernels of csrc/bn_train.hip, forward and backward, bit-identical from step to s
 does, on its own it does nothing: every ``ConvTranspose2d`` deblock that ``bev_deblock_train.deblock_train_routed`` accepts
 (kernel = stride in {1, 2}, no bias, a routed shape) then runs through ``bev_deblock_train.DeblockFunction`` -- forward, input
 gradient and weight gradient on the split-fp16 kernels.  An unrouted deblock, the trailing deblock over the concatenated
-tensor and fractional strides stay modules; BatchNorm + ReLU behind the deblock and ``torch.cat`` stay as they are."""
+tensor and fractional strides stay modules; BatchNorm + ReLU behind the deblock and ``torch.cat`` stay as they are.
+
+``fused_train_down`` (off by default; yaml key ``FUSED_TRAIN_DOWN``) takes effect only where and when ``fused_train`` does, on
+its own it does nothing: the 3 x 3 stride-2 convolution at the head of a block (``ZeroPad2d(1)`` + padding 0, or padding 1)
+that ``bev_down_train.down_train_routed`` accepts then runs through ``bev_down_train.DownFunction`` -- forward on the
+inference kernel, input gradient as four parity phases and weight gradient on the split-fp16 kernels.  An unrouted shape
+stays a module."""
 import torch
 from torch import nn
 
@@ -78,6 +85,7 @@ class BaseBEVBackbone(nn.Module):
         self.fused_train = bool(_get(model_cfg, "FUSED_TRAIN", False))
         self.fused_bn = bool(_get(model_cfg, "FUSED_BN", False))
         self.fused_train_deblocks = bool(_get(model_cfg, "FUSED_TRAIN_DEBLOCKS", False))
+        self.fused_train_down = bool(_get(model_cfg, "FUSED_TRAIN_DOWN", False))
         self._up_filters = [int(c) for c in up_filters[:len(layer_nums)]]
 
     def _deblock_into(self, bev_conv, deblock, x, out, channel):
@@ -132,7 +140,7 @@ class BaseBEVBackbone(nn.Module):
         from .bev_conv_train import run_layers_train
         x, ups = feats.contiguous(memory_format=torch.channels_last), []
         for i, blk in enumerate(self.blocks):
-            x = run_layers_train(blk, x, fused_bn=self.fused_bn)
+            x = run_layers_train(blk, x, fused_bn=self.fused_bn, fused_down=self.fused_train_down)
             data_dict["spatial_features_%dx" % int(feats.shape[2] / x.shape[2])] = x
             ups.append(run_layers_train(self.deblocks[i], x, fused_bn=self.fused_bn, fused_deblocks=self.fused_train_deblocks)
                        if len(self.deblocks) > 0 else x)

@@ -13,7 +13,8 @@ The weights are repacked on every call (they change every step).  Every layer th
 the 1 x 1 deblock, the transposed deblock) stays a torch module: ``run_layers_train`` runs a stack on channels-last tensors and
 sends the ``train_routed`` convolutions through the Function.  With ``fused_deblocks=True`` the transposed deblocks that
 ``bev_deblock_train.deblock_train_routed`` accepts run through ``bev_deblock_train.DeblockFunction`` (the same kernels with
-other tap sets); the stride-2 layer always stays a module.  BatchNorm in training mode and ReLU stay torch modules too
+other tap sets).  The stride-2 layer stays a module unless ``fused_down=True`` and ``bev_down_train.down_train_routed`` accepts
+it: then it runs through ``bev_down_train.DownFunction`` (never through ``conv3x3``).  BatchNorm in training mode and ReLU stay torch modules too
 unless the modules' second switch, ``fused_bn``, is on: then ``run_layers_train(..., fused_bn=True)`` sends every BatchNorm2d
 that ``bn_train.bn_routed`` accepts, with the ReLU behind it, through ``bn_train.BnReluFunction`` (csrc/bn_train.hip).
 
@@ -133,20 +134,23 @@ def conv3x3(conv, x):
     return Conv3x3Function.apply(x, conv.weight, bev_conv._pair(conv.dilation)[0])
 
 
-def run_layers_train(layers, x, fused_bn=False, fused_deblocks=False):
+def run_layers_train(layers, x, fused_bn=False, fused_deblocks=False, fused_down=False):
     """A Conv / BatchNorm / ReLU stack (`layers`: the modules in order) on a channels-last tensor with autograd on: every
     routed convolution through ``Conv3x3Function``, every other module (BatchNorm2d / SyncBatchNorm in training mode and ReLU
     included) as the torch module it is, on the same channels-last tensors.  With `fused_bn`, a BatchNorm2d that
     ``bn_train.bn_routed`` accepts runs through ``bn_train.bn_relu`` together with the ``nn.ReLU`` behind it (in place or not;
     without one: ``relu=False``); every other BatchNorm and ReLU stays a module.  With `fused_deblocks`, a ConvTranspose2d that
     ``bev_deblock_train.deblock_train_routed`` accepts runs through ``bev_deblock_train.DeblockFunction``; every other one
-    stays a module."""
+    stays a module.  With `fused_down`, a 3 x 3 stride-2 Conv2d with padding 1 (or a ZeroPad2d(1) + padding-0 pair) that
+    ``bev_down_train.down_train_routed`` accepts runs through ``bev_down_train.DownFunction``."""
     layers = list(layers)
     i, n = 0, len(layers)
     if fused_bn:
         from . import bn_train
     if fused_deblocks:
         from . import bev_deblock_train
+    if fused_down:
+        from . import bev_down_train
     while i < n:
         m = layers[i]
         if fused_bn and bn_train.bn_routed(m):
@@ -160,6 +164,14 @@ def run_layers_train(layers, x, fused_bn=False, fused_deblocks=False):
             i += 2
         elif isinstance(m, nn.Conv2d) and train_routed(m):
             x = conv3x3(m, x)
+            i += 1
+        elif fused_down and isinstance(m, nn.ZeroPad2d) and tuple(m.padding) == (1, 1, 1, 1) and i + 1 < n \
+                and isinstance(layers[i + 1], nn.Conv2d) and bev_conv._pair(layers[i + 1].padding) == (0, 0) \
+                and bev_down_train.down_train_routed(layers[i + 1], 1):
+            x = bev_down_train.down(layers[i + 1], x)
+            i += 2
+        elif fused_down and isinstance(m, nn.Conv2d) and bev_down_train.down_train_routed(m):
+            x = bev_down_train.down(m, x)
             i += 1
         elif fused_deblocks and isinstance(m, nn.ConvTranspose2d) and bev_deblock_train.deblock_train_routed(m):
             x = bev_deblock_train.deblock(m, x)

@@ -13,7 +13,10 @@
 //     (split_wgrad.hip.h: a GEMM over pixels in slices, partial slabs in a workspace, added in slice order);
 //   * mssvt_bev_deblock_*, the backward of the transposed deblocks whose kernel equals their stride s in {1, 2}: the weight
 //     gradient is the same GEMM with the phases (dy, dx) as taps (BW_PHASES), the input gradient is k_split_conv over dY with
-//     the weight tensor (cin, cout, s, s) packed as the Conv2d weight (out, in, ky, kx) it already is: s x s taps at stride s.
+//     the weight tensor (cin, cout, s, s) packed as the Conv2d weight (out, in, ky, kx) it already is: s x s taps at stride s;
+//   * mssvt_bev_down_*, the backward of the 3 x 3 stride-2 layer (zero padding 1): the weight gradient is the same GEMM over
+//     the OUTPUT pixels with X read at (2 oy + ky - 1, 2 ox + kx - 1) (BW_DOWN), the input gradient is k_split_conv over dY as
+//     the four parity phases of dX in one launch (BC_DOWN2: 4 + 2 + 2 + 1 taps, the 9 taps of the weight each used once).
 #include "split_conv.hip.h"
 #include "split_wgrad.hip.h"
 
@@ -236,6 +239,80 @@ extern "C" int mssvt_bev_deblock_dgrad(const float *dy, const float *weight, int
                                                            CI / BC_NS(CI), stride, stride, 1, edy, 1, 0, dx, nullptr, 0, 0, st); \
     }
     BD_GO(128, 256) BD_GO(256, 256) BD_GO(32, 64) BD_GO(64, 32)
+#undef BD_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// ---- the backward of Conv2d(cin, cout, 3, stride = 2, padding = 1): x / dx (B, H, W, cin), dy (B, Ho, Wo, cout) -------------------
+extern "C" int mssvt_bev_down_train_supported(int cin, int cout) { return bw_down_shape(cin, cout) ? 1 : 0; }
+
+extern "C" int mssvt_bev_down_wgrad_slice_pixels(int cin, int cout) { return bw_down_shape(cin, cout) ? bw_down_slice_pixels(cin) : 0; }
+
+// [words of x: B H W int32, padded to 256 bytes][words of dy: B Ho Wo, padded][slices x 9 slabs of (cout, cin) f32]
+extern "C" long long mssvt_bev_down_wgrad_workspace_bytes(int B, int H, int W, int cin, int cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || !bw_down_shape(cin, cout) || bc_too_many_pixels(B, H, W)) return 0;
+    const long long M = (long long)B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1), slice = bw_down_slice_pixels(cin);
+    return bw_round256(4ll * B * H * W) + bw_round256(4 * M) + (M + slice - 1) / slice * 9 * cin * cout * 4;
+}
+
+extern "C" int mssvt_bev_down_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int cout, float *dw,
+                                    void *workspace, void *stream) {
+    if (!x || !dy || !dw || !workspace || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || bc_misaligned(x) ||
+        bc_misaligned(dy) || bc_misaligned(dw) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!bw_down_shape(cin, cout) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long long Mx = (long long)B * H * W, M = (long long)B * Ho * Wo;
+    int *ex = reinterpret_cast<int *>(workspace), *edy = ex + bw_round256(4 * Mx) / 4;
+    float *slab = reinterpret_cast<float *>(edy + bw_round256(4 * M) / 4);
+    // bw_launch(tapped, plain, .., cols, rows, ..): rows = cout (dy, the plain operand), columns = cin (x, read at the tap's pixel)
+#define BD_GO(CI, CO, TILE)                                                                                                  \
+    if (cin == CI && cout == CO) {                                                                                           \
+        int status = bc_expmap<CI, CI / 4>(x, Mx, ex, st);                                                                   \
+        if (status != MSSVT_OK) return status;                                                                               \
+        status = bc_expmap<CO, CO / 4>(dy, M, edy, st);                                                                      \
+        if (status != MSSVT_OK) return status;                                                                               \
+        return bw_launch<TILE, BW_DOWN>(x, dy, Ho, Wo, (int)M, cin, cout, 2, 9, bw_down_slice_pixels(cin), ex, edy, slab, dw, \
+                                        st, H, W);                                                                           \
+    }
+    BD_GO(128, 256, 128) BD_GO(32, 64, 32)
+#undef BD_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// the blob of the four phase convolutions cout -> cin, 9 taps in all (one header record: 64 bytes, scale, shift, the blocks)
+static long long bdn_blob_bytes(int cin, int cout) { return BC_HDR(1) + 8ll * cin + 4ll * 9 * cin * cout; }
+
+// [words of dy: B Ho Wo int32, padded to 256 bytes][the blob]
+extern "C" long long mssvt_bev_down_dgrad_workspace_bytes(int B, int H, int W, int cin, int cout) {
+    if (B <= 0 || H <= 0 || W <= 0 || !bw_down_shape(cin, cout) || bc_too_many_pixels(B, H, W)) return 0;
+    return bw_round256(4ll * B * ((H - 1) / 2 + 1) * ((W - 1) / 2 + 1)) + bdn_blob_bytes(cin, cout);
+}
+
+extern "C" int mssvt_bev_down_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int cout, float *dx,
+                                    void *workspace, void *stream) {
+    if (!dy || !weight || !dx || !workspace || B <= 0 || H <= 0 || W <= 0 || cin <= 0 || cout <= 0 || bc_misaligned(dy) ||
+        bc_misaligned(weight) || bc_misaligned(dx) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!bw_down_shape(cin, cout) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const int Ho = (H - 1) / 2 + 1, Wo = (W - 1) / 2 + 1;
+    const long long M = (long long)B * Ho * Wo;
+    int *edy = reinterpret_cast<int *>(workspace);
+    void *blob = edy + bw_round256(4 * M) / 4;
+    // four convolutions of CO input and CI output channels over dy (B, Ho, Wo), one per parity of dx's pixel: BC_DOWN2
+#define BD_GO(CI, CO)                                                                                                       \
+    if (cin == CI && cout == CO) {                                                                                          \
+        int status = bc_pack(weight, 3, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 3, CO, CI, 0, BC_NS(CI),          \
+                             CI / BC_NS(CI), 0, 1, blob, st);                                                               \
+        if (status != MSSVT_OK) return status;                                                                              \
+        status = bc_expmap<CO, CO / 4>(dy, M, edy, st);                                                                     \
+        if (status != MSSVT_OK) return status;                                                                              \
+        return bc_launch<CO, BC_NS(CI), 0, false, BC_DOWN2>(dy, CO, 0, Ho, Wo, H, W, (int)M, blob, CI / BC_NS(CI), 3, 2, 1, \
+                                                            edy, 1, 0, dx, nullptr, 0, 0, st);                              \
+    }
+    BD_GO(128, 256) BD_GO(32, 64)
 #undef BD_GO
     return MSSVT_E_TOOLARGE;
 }

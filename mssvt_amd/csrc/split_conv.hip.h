@@ -78,7 +78,7 @@ struct bc_geom {
     static constexpr size_t LDS = 2 * (size_t)2 * IMG * 16;  // two buffers of a hi and a lo image
 };
 
-enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2 };
+enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2, BC_DOWN2 };
 // OUT: y (M, nsl NS) rows; rows and eout [pixel][nsl], the largest |y| of the pixel's slice as bits; slice sl's k <= 16 maps
 // planar at float kbase B H W; rows of `ystride` floats of which the layer owns channels [ybase, ybase + nsl NS) (a slice of a
 // wider tensor; ystride % 4 == ybase % 4 == 0 keeps the stores aligned); UP2: the four phases of a 2 x 2 stride-2 transposed
@@ -87,6 +87,14 @@ enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2 };
 // channel ybase + cs NS.  The UP2 grid is one-dimensional: block id = ((pixel block / 8) nsl + sl) 8 + pixel block % 8, so the
 // nsl slices that read one input tile follow each other at a distance of 8 ids (consecutive ids go round the chiplets: the
 // slices of a tile share one L2); pixel blocks are padded to a multiple of 8 and a padding block leaves at once.
+// DOWN2: the input gradient of a 3 x 3 stride-2 convolution (zero padding 1) as its four parity phases in ONE launch, grid
+// (pixel blocks of the largest phase, nsl, 4).  x = dY on the H x W grid (CIN = the layer's output channels), y = dX on the
+// Ho_ x Wo_ grid of the layer's INPUT (H = (Ho_ + 1) / 2), M = B H W.  blockIdx.z = 3 - (2 py + px): phase (py, px) is the
+// (1 + py) x (1 + px) convolution at stride 1 without padding over dY whose output pixel (j, i) is row (b, 2 j + py, 2 i + px)
+// of dX -- tap (ty, tx) reads dY (j + ty, i + tx), zeros beyond the grid (the ky = 0 tap of the last row of an even Ho_).  The
+// phase grid is Ho_ / 2 (py = 1) or H (py = 0) rows by Wo_ / 2 or W columns: an empty phase (Ho_ = 1 or Wo_ = 1) and the blocks
+// beyond a smaller phase leave at once; the 4-tap phase is dealt first.  The blob holds the layer's 9 taps in phase order
+// (k_split_pack, transposed = 3) under one header record; ksize_, stride_ and dil_ are not read.
 
 // TAPS 0: ksize x ksize taps (3: padding = dil, 1: none) at `stride` / `dil`, output Ho x Wo;  TAPS 3: 3 x 3, stride 1,
 // dilation 1, Ho = H, Wo = W as constants (those five arguments are not read).
@@ -95,7 +103,7 @@ enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2 };
 // when egroups > 1 (else word 0), and header record sl.
 template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
 __global__ void __launch_bounds__(BC_THREADS, 1)
-    k_split_conv(const float *x, int xstride_, int gin, int H, int W, int Ho_, int Wo_, int M, const unsigned char *blob, int nsl,
+    k_split_conv(const float *x, int xstride_, int gin, int H, int W, int Ho_, int Wo_, int M_, const unsigned char *blob, int nsl,
                  int ksize_, int stride_, int dil_, const int *emap, int egroups_, int relu, float *y, int *eout, int ystride,
                  int ybase) {
     using G = bc_geom<CIN, NS>;
@@ -106,19 +114,26 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     h16x8 *lds = reinterpret_cast<h16x8 *>(bc_lds);  // two buffers of 2 IMG fragments
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / MSSVT_WAVE);
-    const int ksize = TAPS ? TAPS : ksize_, stride = TAPS ? 1 : stride_, dil = TAPS ? 1 : dil_;
-    const int Ho = TAPS ? H : Ho_, Wo = TAPS ? W : Wo_, HWo = Ho * Wo;
-    const int nstages = ksize * ksize * CHUNKS, pad = ksize == 3 ? dil : 0;
+    constexpr bool DN = OUT == BC_DOWN2;
+    const int py = DN ? (3 - (int)blockIdx.z) >> 1 : 0, px = DN ? (3 - (int)blockIdx.z) & 1 : 0;  // DOWN2: the phase
+    const int ksize = DN ? 1 : TAPS ? TAPS : ksize_, stride = (DN || TAPS) ? 1 : stride_, dil = (DN || TAPS) ? 1 : dil_;
+    const int ksy = DN ? 1 + py : ksize, ksx = DN ? 1 + px : ksize;  // taps in y and in x
+    const int Ho = DN ? (py ? Ho_ / 2 : H) : TAPS ? H : Ho_, Wo = DN ? (px ? Wo_ / 2 : W) : TAPS ? W : Wo_, HWo = Ho * Wo;
+    const int M = DN ? (M_ / (H * W)) * HWo : M_;  // DOWN2: the phase's pixels
+    const int nstages = ksy * ksx * CHUNKS, pad = ksize == 3 ? dil : 0;
     const int pb = OUT == BC_UP2 ? (int)(blockIdx.x / (8 * nsl)) * 8 + (int)(blockIdx.x % 8) : (int)blockIdx.x;  // pixel block
     const int sl = OUT == BC_UP2 ? (int)(blockIdx.x / 8) % nsl : (int)blockIdx.y;
-    if (OUT == BC_UP2 && pb * BC_BLOCK_PIXELS >= M) return;  // (the whole workgroup, before any barrier)
+    if ((OUT == BC_UP2 || DN) && pb * BC_BLOCK_PIXELS >= M) return;  // (the whole workgroup, before any barrier)
     const int cout = nsl * NS, hdr = SLICED ? BC_HDR(nsl) : BC_HDR(1);
     const int xstride = SLICED ? xstride_ : CIN, cbase = SLICED ? sl * gin : 0;
     const int egroups = SLICED ? egroups_ : 1, eoff = egroups > 1 ? sl : 0;
     const float *rec = reinterpret_cast<const float *>(blob + (SLICED ? (size_t)sl * BC_REC_BYTES : 0));
     const float w_un = rec[1];
     const float *scale = reinterpret_cast<const float *>(blob + hdr) + sl * NS, *shift = scale + cout;
-    const h16x8 *wsrc = reinterpret_cast<const h16x8 *>(blob + hdr + (size_t)cout * 8) + (size_t)sl * nstages * 2 * IMG;
+    // DOWN2: a slice holds all 9 taps, the phase's own start at tap 0 (2 x 2), 4 (2 x 1), 6 (1 x 2), 8 (1 x 1)
+    const int tap0 = DN ? (py ? (px ? 0 : 4) : (px ? 6 : 8)) : 0, slice_stages = DN ? 9 * CHUNKS : nstages;
+    const h16x8 *wsrc = reinterpret_cast<const h16x8 *>(blob + hdr + (size_t)cout * 8) +
+                        ((size_t)sl * slice_stages + tap0 * CHUNKS) * 2 * IMG;
     // block 0 of the weights -> LDS buffer 0
 #pragma unroll
     for (int i = 0; i < FR; ++i) {
@@ -141,8 +156,8 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
         // the pixel's power of two: the largest exponent over its receptive field (all taps inside the image)
         int e = 0;
         if (live[j])
-            for (int ky = 0; ky < ksize; ++ky)
-                for (int kx = 0; kx < ksize; ++kx) {
+            for (int ky = 0; ky < ksy; ++ky)
+                for (int kx = 0; kx < ksx; ++kx) {
                     const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
                     if (iy >= 0 && iy < H && ix >= 0 && ix < W) e = max(e, emap[(size_t)(img[j] + iy * W + ix) * egroups + eoff]);
                 }
@@ -159,7 +174,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
     float4 xa[2][2];
     auto load_rows = [&](int st, int P) {
         const int tap = st / CHUNKS, chunk = st - tap * CHUNKS;
-        const int ky = (tap >= ksize) + (tap >= 2 * ksize), kx = tap - ky * ksize;
+        const int ky = (tap >= ksx) + (tap >= 2 * ksx), kx = tap - ky * ksx;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
@@ -220,8 +235,12 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
         if (OUT != BC_ROWS_WORDS && !live[j]) continue;  // (with words the whole wave takes part in the exchange below)
         const int m = pb * BC_BLOCK_PIXELS + wv * BC_WAVE_PIXELS + 16 * j + la, mc = live[j] ? m : 0;
         int top = 0;  // the largest |y| of the lane's columns, as bits
-        size_t row = 0;  // INTO / UP2: the first float of the lane's pixel and slice in y
+        size_t row = 0;  // INTO / UP2 / DOWN2: the first float of the lane's pixel and slice in y
         if (OUT == BC_ROWS_INTO) row = (size_t)mc * ystride + ybase + sl * NS;
+        if (DN) {  // pixel (j, i) of the phase's grid is pixel (2 j + py, 2 i + px) of the Ho_ x Wo_ tensor
+            const int b = mc / HWo, r = mc - b * HWo, j2 = r / Wo, i2 = r - j2 * Wo;
+            row = (((size_t)b * Ho_ + 2 * j2 + py) * Wo_ + 2 * i2 + px) * cout + sl * NS;
+        }
         if (OUT == BC_UP2) {  // (Ho = H, Wo = W: the launch is a 1 x 1 layer over the input pixels)
             const int nc = nsl / 4, ph = sl / nc, b = mc / HWo, r = mc - b * HWo, iy = r / Wo, ix = r - iy * Wo;
             row = (((size_t)b * 2 * Ho + 2 * iy + (ph >> 1)) * (2 * Wo) + 2 * ix + (ph & 1)) * ystride + ybase + (sl - ph * nc) * NS;
@@ -248,7 +267,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
                     if (4 * g + i < kcols) out[(size_t)(4 * g + i) * HWo] = o[i];
-            } else if (OUT == BC_ROWS_INTO || OUT == BC_UP2) {
+            } else if (OUT == BC_ROWS_INTO || OUT == BC_UP2 || DN) {
                 *reinterpret_cast<float4 *>(y + row + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
             } else {
                 *reinterpret_cast<float4 *>(y + (size_t)mc * cout + sl * NS + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
@@ -271,7 +290,7 @@ static int bc_launch(const float *x, int xstride, int gin, int H, int W, int Ho,
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     if (e != hipSuccess) return (int)e;
     const int nblocks = divup(M, BC_BLOCK_PIXELS);
-    const dim3 grid = OUT == BC_UP2 ? dim3((nblocks + 7) / 8 * 8 * nsl) : dim3(nblocks, nsl);
+    const dim3 grid = OUT == BC_UP2 ? dim3((nblocks + 7) / 8 * 8 * nsl) : dim3(nblocks, nsl, OUT == BC_DOWN2 ? 4 : 1);
     kernel<<<grid, BC_THREADS, LDS, st>>>(x, xstride, gin, H, W, Ho, Wo, M, reinterpret_cast<const unsigned char *>(packed), nsl,
                                           ksize, stride, dil, emap, egroups, relu, y, eout, ystride, ybase);
     return mssvt_launch_status();
@@ -319,7 +338,10 @@ static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long
 // one thread per operand fragment: (slice, stage = (tap, chunk), P, t, lane) -> 8 weights of output channel n = slice ns +
 // 16 t + lane % 16 of the tensor (zeros beyond k), c = chunk KC + 32 P + 8 (lane / 16) .., split into the hi and the lo image
 // of the stage's block.  The tensor is a Conv2d weight (k, cin, ksize, ksize), or a ConvTranspose2d weight: `transposed` 1:
-// (cin, k, 1, 1); 2 (ksize = 1): (cin, k / 4, 2, 2), column n = phase (dy 2 + dx) k / 4 + output channel (the UP2 form)
+// (cin, k, 1, 1); 2 (ksize = 1): (cin, k / 4, 2, 2), column n = phase (dy 2 + dx) k / 4 + output channel (the UP2 form);
+// 3 (ksize = 3): the Conv2d weight (cin, k, 3, 3) of the layer whose INPUT gradient the blob computes (the DOWN2 form) -- the
+// channel axes swap and stage tap s is tap (ky, kx) of the tensor in phase order: (2,2) (2,0) (0,2) (0,0) | (2,1) (0,1) |
+// (1,2) (1,0) | (1,1), the dY offset (0 or 1) of a tap being its place in its phase's list
 static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int transposed, int ksize, int cin, int k, int ns,
                                                            int nsl, int sl, int n_slices, int hdr, unsigned char *blob) {
     const int KC = BC_KC(cin), KS = KC / 32, NT = ns / 16, CHUNKS = cin / KC, IMG = KS * NT * 64;
@@ -335,6 +357,7 @@ static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int t
 #pragma unroll
     for (int i = 0; i < 8; ++i)
         v[i] = n >= k              ? 0.f
+               : transposed == 3 ? w[((size_t)(c0 + i) * k + n) * 9 + (int)((0x435170268ull >> (4 * tap)) & 15)]
                : transposed == 2 ? w[((size_t)(c0 + i) * (k / 4) + n % (k / 4)) * 4 + n / (k / 4)]
                : transposed      ? w[(size_t)(c0 + i) * k + n]
                                  : w[((size_t)n * cin + c0 + i) * ntaps + tap];

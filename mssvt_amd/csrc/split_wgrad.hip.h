@@ -28,7 +28,11 @@
 //                  dW[c, n, dy, dx] = sum over (b, iy, ix) of X[b, iy, ix, c] dY[b, s iy + dy, s ix + dx, n]:
 //              plain = X (rows c, the B H W input pixels are the reduction), tapped = dY (columns n) of the (B, s H, s W) grid
 //              at (s iy + dy, s ix + dx), s s taps (the phases; every tapped pixel lies inside).  dW (cin, cout, s, s) is again
-//              [row][column][tap]: the same second launch writes it.
+//              [row][column][tap]: the same second launch writes it;
+//   BW_DOWN    the 3 x 3 layer at stride 2 (dilation 1, zero padding 1) over an input of Ht x Wt pixels,
+//                  dW[o, c, ky, kx] = sum over (b, oy, ox) of dY[b, oy, ox, o] X[b, 2 oy + ky - 1, 2 ox + kx - 1, c]:
+//              plain = dY (rows o, the B Ho Wo OUTPUT pixels are the reduction, H x W = Ho x Wo), tapped = X (columns c) of the
+//              (B, Ht, Wt) grid, 9 taps; a tap that leaves the image loads neither row, as in BW_TAPS3.
 #pragma once
 #include "split_conv.hip.h"
 
@@ -50,6 +54,9 @@ static bool bw_deblock_shape(int stride, int cin, int cout) {
                        : stride == 2 && ((cin == 256 && cout == 256) || (cin == 64 && cout == 32));
 }
 static int bw_deblock_slice_pixels(int cin) { return cin >= 256 ? 2048 : cin >= 128 ? 1024 : 256; }
+// the stride-2 3 x 3 layer (cin, cout): slices of OUTPUT pixels
+static bool bw_down_shape(int cin, int cout) { return (cin == 128 && cout == 256) || (cin == 32 && cout == 64); }
+static int bw_down_slice_pixels(int cin) { return cin >= 128 ? 2048 : 256; }
 static long long bw_round256(long long n) { return (n + 255) / 256 * 256; }
 
 template <int C>
@@ -62,30 +69,36 @@ struct bw_geom {
     static_assert(ITEMS % THREADS == 0 && NT % TM == 0 && NT % TN == 0 && RS % 16 == 0 && WAVES <= 8, "tiling");
 };
 
-enum { BW_TAPS3, BW_PHASES };
+enum { BW_TAPS3, BW_PHASES, BW_DOWN };
 // tapped_op: the TAPPED operand, pixels of `cols` floats (the tile's columns); plain_op: the PLAIN operand, M = B H W pixels of
 // `rows` floats (the tile's rows); etapped / eplain: their k_split_expmap words; slab [slice][tap][rows][cols].  H, W: the grid
-// of the reduction pixels; step: the dilation (BW_TAPS3) or the stride s (BW_PHASES: tapped_op then has s s M pixels).
-// BW_TAPS3: plain = dY, rows = cout, tapped = X, cols = cin;  BW_PHASES: plain = X, rows = cin, tapped = dY, cols = cout.
+// of the reduction pixels; step: the dilation (BW_TAPS3) or the stride s (BW_PHASES: tapped_op then has s s M pixels); Ht, Wt:
+// the grid of the tapped operand (read by BW_DOWN alone: the other maps derive it from H, W and step).
+// BW_TAPS3, BW_DOWN: plain = dY, rows = cout, tapped = X, cols = cin;  BW_PHASES: plain = X, rows = cin, tapped = dY, cols = cout.
 // grid (slices, (rows / C) (cols / C), taps)
 template <int C, int MAP>
 __global__ void __launch_bounds__(bw_geom<C>::THREADS)
     k_split_wgrad(const float *tapped_op, const float *plain_op, int H, int W, int M, int cols, int rows, int step, int slice,
-                  const int *etapped, const int *eplain, float *slab) {
+                  const int *etapped, const int *eplain, float *slab, int Ht, int Wt) {
     using G = bw_geom<C>;
     constexpr int TM = G::TM, TN = G::TN, RS = G::RS, IMG = G::IMG, BUF = G::BUF, IT = G::IT, THREADS = G::THREADS;
     extern __shared__ __attribute__((aligned(16))) char bw_lds[];
     const int tid = threadIdx.x, lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(tid / MSSVT_WAVE);
     const int s = blockIdx.x, tiles = cols / C, co0 = ((int)blockIdx.y / tiles) * C, ci0 = ((int)blockIdx.y % tiles) * C;
-    const int tap = blockIdx.z, ntaps = gridDim.z, kdim = MAP == BW_TAPS3 ? 3 : step, ky = tap / kdim, kx = tap - kdim * ky;
-    const int oy = MAP == BW_TAPS3 ? (ky - 1) * step : ky, ox = MAP == BW_TAPS3 ? (kx - 1) * step : kx;
+    const int tap = blockIdx.z, ntaps = gridDim.z, kdim = MAP == BW_PHASES ? step : 3, ky = tap / kdim, kx = tap - kdim * ky;
+    const int oy = MAP == BW_TAPS3 ? (ky - 1) * step : MAP == BW_DOWN ? ky - 1 : ky;
+    const int ox = MAP == BW_TAPS3 ? (kx - 1) * step : MAP == BW_DOWN ? kx - 1 : kx;
     const int HW = H * W;
     const int m0 = s * slice, m1 = M - m0 > slice ? m0 + slice : M;  // the slice's pixels [m0, m1): may span two samples
     // the pixel the tap reads for reduction pixel m, or -1 outside the image (a phase never leaves it: s^2 M < 2^31)
     auto tapped = [&](int m) {
         const int b = m / HW, r = m - b * HW, y = r / W;
         if (MAP == BW_PHASES) return ((b * H + y) * step + oy) * (step * W) + (r - y * W) * step + ox;
+        if (MAP == BW_DOWN) {  // (B Ht Wt < 2^31: the entry point's check)
+            const int ty = 2 * y + oy, tx = 2 * (r - y * W) + ox;
+            return (ty >= 0 && ty < Ht && tx >= 0 && tx < Wt) ? (b * Ht + ty) * Wt + tx : -1;
+        }
         const int iy = y + oy, ix = r - y * W + ox;
         return (iy >= 0 && iy < H && ix >= 0 && ix < W) ? b * HW + iy * W + ix : -1;
     };
@@ -220,14 +233,15 @@ static __global__ void __launch_bounds__(256) k_split_wgrad_sum(const float *sla
 // (the kernel's arguments; dw is (rows, cols, taps))
 template <int C, int MAP>
 static int bw_launch(const float *tapped_op, const float *plain_op, int H, int W, int M, int cols, int rows, int step, int ntaps,
-                     int slice, const int *etapped, const int *eplain, float *slab, float *dw, hipStream_t st) {
+                     int slice, const int *etapped, const int *eplain, float *slab, float *dw, hipStream_t st, int Ht = 0,
+                     int Wt = 0) {
     using G = bw_geom<C>;
     const auto kernel = k_split_wgrad<C, MAP>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     if (e != hipSuccess) return (int)e;
     const int nslices = divup(M, slice);
     kernel<<<dim3(nslices, (rows / C) * (cols / C), ntaps), G::THREADS, G::LDS, st>>>(tapped_op, plain_op, H, W, M, cols, rows, step, slice,
-                                                                                   etapped, eplain, slab);
+                                                                                   etapped, eplain, slab, Ht, Wt);
     int status = mssvt_launch_status();
     if (status != MSSVT_OK) return status;
     k_split_wgrad_sum<<<divup(ntaps * cols * rows, 256), 256, 0, st>>>(slab, nslices, cols, rows, ntaps, dw);

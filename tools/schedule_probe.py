@@ -152,6 +152,18 @@ def main(out_path):
         assert 2 * hw[0] * hw[1] > bev_deblock_train.slice_pixels(s, cin, cout)
         out["bev_deblock_wgrad_s%d_%d_%d" % (s, cin, cout)] = bev_deblock_train.deblock_wgrad(xr, gr, s).cpu().numpy()
         out["bev_deblock_dgrad_s%d_%d_%d" % (s, cin, cout)] = bev_deblock_train.deblock_dgrad(gr, wr, s).cpu().numpy()
+    # --- the stride-2 layer's backward (bev_down_train.py): the weight gradient with the stride-2 tap map over more than one
+    # slice (2 x 1 tiles of 128, and the narrow shape), and the input gradient as four parity phases in one launch (the
+    # 256 -> 128 form: two input chunks, up to four taps) on an even x odd input
+    from mssvt_amd import bev_down_train
+    for cin, cout, hw in ((128, 256, (92, 95)), (32, 64, (46, 47))):
+        ho, wo = bev_down_train.out_size(*hw)
+        xr = torch.randn(2, hw[0], hw[1], cin, generator=g).to(DEV).permute(0, 3, 1, 2)
+        gr = torch.randn(2, ho, wo, cout, generator=g).to(DEV).permute(0, 3, 1, 2)
+        wr = torch.randn(cout, cin, 3, 3, generator=g).to(DEV)
+        assert 2 * ho * wo > bev_down_train.slice_pixels(cin, cout)
+        out["bev_down_wgrad_%d_%d" % (cin, cout)] = bev_down_train.down_wgrad(xr, gr).cpu().numpy()
+        out["bev_down_dgrad_%d_%d" % (cin, cout)] = bev_down_train.down_dgrad(gr, wr, hw[0], hw[1]).cpu().numpy()
     # --- csrc/head_conv.hip: shared layer, trunk and finals at the golden (64 -> 32) and the product (512 -> 64) channel counts:
     # one and four input chunks, one to four column tiles, the planar 16-column tile
     from mssvt_amd import head_conv
