@@ -1253,6 +1253,57 @@ int mssvt_head_conv_trunk(const float *x, int B, int H, int W, int s, int nb, co
 int mssvt_head_conv_finals(const float *x, int B, int H, int W, int s, int nb, const void *packed, const int *exp_in,
                            float *y, void *stream);
 
+/* CenterHead's shared layer and trunk in TRAINING mode, forward and backward (csrc/head_conv.hip, csrc/split_conv.hip.h,
+ * csrc/split_wgrad.hip.h; ref center_head.py :76-84, :11-46).  The layers are the plain convolutions y = conv3x3(x, W) + bias
+ * (stride 1, zero padding 1); their BatchNorm2d + ReLU are not part of these calls.  All tensors channels-last f32.
+ * cin in {64, 256, 384, 512}, s in {32, 64}, 1 <= nb <= 64 branches: mssvt_head_conv_train_supported.
+ *   shared  mssvt_head_conv_shared_train: x (B, H, W, cin) -> y (B, H, W, s); packed = mssvt_head_conv_shared_pack's blob with
+ *             the BatchNorm pointers NULL (scale 1, shift = bias); exp_workspace (B H W) int32 is written here.
+ *           mssvt_head_conv_shared_dgrad: dx (B, H, W, cin) = the convolution s -> cin over dy with the taps of weight
+ *             (s, cin, 3, 3) rotated by 180 degrees and the channel axes swapped; the tensor is packed inside the call
+ *             (workspace: roundup(4 B H W, 256) + 64 + 8 cin + 36 cin s bytes).
+ *           mssvt_head_conv_shared_wgrad: dw (s, cin, 3, 3), mssvt_bev_conv_wgrad's kernel and arithmetic on s x s tiles of
+ *             (s, cin); the pixels are cut into slices of mssvt_head_conv_train_wgrad_slice_pixels(cin, s) (the trunk: (s, s); workspace: 2 roundup(4 B H W,
+ *             256) + slices 9 cin s 4 bytes).
+ *   trunk   mssvt_head_conv_trunk_train: y (B, H, W, s) -> t [nb][B H W][s], BRANCH-MAJOR: branch b's output is the dense
+ *             (B, H, W, s) tensor at float b B H W s; packed = mssvt_head_conv_trunk_pack's blob, BatchNorm pointers NULL.
+ *           mssvt_head_conv_trunk_dgrad: dy (B, H, W, s) = sum over b of rot(W_b) applied to dT_b, one launch, one accumulation
+ *             chain per element; one power of two per output pixel over its receptive field and ALL branches, one for all
+ *             weights (workspace: roundup(4 nb B H W, 256) + 64 + 8 s + 36 s s nb bytes).
+ *           mssvt_head_conv_trunk_wgrad: dw [nb][s][s][3][3]; per slice, every branch's dT_b rows are normalised by that
+ *             branch's own power of two (workspace: roundup(4 B H W, 256) + roundup(4 nb B H W, 256) + slices 9 nb s s 4).
+ *   bias    mssvt_head_conv_bgrad: db [nb][s] = the sums over pixels of dT_b (the shared layer: nb = 1), in pieces of
+ *             mssvt_head_conv_train_bias_piece_rows rows: each of the 1024 / s threads of a column adds its rows (every
+ *             1024 / s-th) in row order, those threads are added in order, the pieces in piece order (workspace: pieces nb s 4).
+ * host_dts / host_dys / host_weights: HOST arrays of nb device pointers (the tensors autograd hands back, dT_b (B, H, W, s),
+ * and the weights W_b (s, s, 3, 3)), read during the call and handed to the kernels by value.
+ * No float atomics, one writer per output element, bit-identical from call to call whatever the workspaces held, no host read;
+ * scaling an operand by a power of two scales the result bit for bit.  *_workspace_bytes: 0 where the call would refuse.
+ * Null / unaligned (16 bytes) pointers and sizes < 1: MSSVT_E_BADARG; sizes outside the sets above, nb > 64,
+ * B H W >= 2^31 - 1024: MSSVT_E_TOOLARGE; neither launches anything.                                                      */
+int mssvt_head_conv_train_supported(int cin, int s, int nb);
+int mssvt_head_conv_train_wgrad_slice_pixels(int cin, int s);
+int mssvt_head_conv_train_bias_piece_rows(int s);
+int mssvt_head_conv_shared_train(const float *x, int B, int H, int W, int cin, int s, const void *packed, int *exp_workspace,
+                                 float *y, void *stream);
+long long mssvt_head_conv_shared_dgrad_workspace_bytes(int B, int H, int W, int cin, int s);
+int mssvt_head_conv_shared_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int s, float *dx,
+                                 void *workspace, void *stream);
+long long mssvt_head_conv_shared_wgrad_workspace_bytes(int B, int H, int W, int cin, int s);
+int mssvt_head_conv_shared_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int s, float *dw,
+                                 void *workspace, void *stream);
+long long mssvt_head_conv_bgrad_workspace_bytes(int B, int H, int W, int s, int nb);
+int mssvt_head_conv_bgrad(const float *const *host_dys, int B, int H, int W, int s, int nb, float *db, void *workspace,
+                          void *stream);
+int mssvt_head_conv_trunk_train(const float *y, int B, int H, int W, int s, int nb, const void *packed, int *exp_workspace,
+                                float *t, void *stream);
+long long mssvt_head_conv_trunk_dgrad_workspace_bytes(int B, int H, int W, int s, int nb);
+int mssvt_head_conv_trunk_dgrad(const float *const *host_dts, const float *const *host_weights, int B, int H, int W, int s,
+                                int nb, float *dy, void *workspace, void *stream);
+long long mssvt_head_conv_trunk_wgrad_workspace_bytes(int B, int H, int W, int s, int nb);
+int mssvt_head_conv_trunk_wgrad(const float *y, const float *const *host_dts, int B, int H, int W, int s, int nb, float *dw,
+                                void *workspace, void *stream);
+
 /* DynamicVFE's two PFN layers in eval mode as two launches (csrc/pfn_fused.hip; ref
  * pcdet/models/backbones_3d/vfe/dynamic_vfe.py:96-131, PFNLayerV2 :14-52), default configuration: 5 point features + cluster
  * offset + voxel-centre offset (11 inputs), NUM_FILTERS [64, 128].  points (P, stride >= 6) f32 rows [b, x, y, z, f4, f5];

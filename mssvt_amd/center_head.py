@@ -15,14 +15,22 @@ module with its own loss classes (tests/golden/det_head_train.npz: targets, loss
 convolutions of a head that ``head_conv.supported`` covers (every branch ``num_conv == 2`` with at most 16 maps, Cin in {64, 256,
 384, 512}, SHARED_CONV_CHANNEL in {32, 64}, BatchNorm2d with running statistics) run on csrc/head_conv.hip -- the stages that
 ``head_conv.ROUTED`` names -- and produce the same ``pred_dicts``; decoding is unchanged.  Under any other condition, and for
-any other head, the forward is the library's, untouched."""
+any other head, the forward is the library's, untouched.
+
+``fused_train`` (off by default; yaml key ``FUSED_TRAIN``): in training mode with autograd on, an fp32 GPU input and no AMP, the
+shared layer and the first convolution of every branch of a head that ``head_conv_train.train_supported`` covers (the same
+structure and sizes) run forward and backward on csrc/head_conv.hip -- the stages that ``head_conv_train.ROUTED_TRAIN`` names --
+through ``head_conv_train.forward_train``; the last convolutions, every BatchNorm2d and every ReLU stay the modules they are.
+``fused_bn`` (off by default; yaml key ``FUSED_BN``) takes effect only where and when ``fused_train`` does: the BatchNorm2d +
+ReLU pairs behind a routed stage run through ``bn_train.bn_relu`` for the widths of ``head_conv_train.ROUTED_BN``.  Under any
+other condition the forward is exactly the library's."""
 import copy
 
 import numpy as np
 import torch
 from torch import nn
 
-from . import _lib, head_conv, iou3d_nms_utils
+from . import _lib, head_conv, head_conv_train, iou3d_nms_utils
 
 
 def _get(cfg, key, default=None):
@@ -379,6 +387,11 @@ class CenterHead(nn.Module):
         # eval forward without autograd, fp32 on the GPU, no AMP (bev_conv.switch_applies) and a head head_conv.supported
         # covers: the convolutions on csrc/head_conv.hip (the stages head_conv.ROUTED names); anything else: the library
         self.fused_convs = bool(_get(model_cfg, "FUSED_CONVS", False))
+        # training forward with autograd on, fp32 on the GPU, no AMP and a head head_conv_train.train_supported covers: the
+        # shared layer and the trunk through head_conv_train's Functions (the stages ROUTED_TRAIN names); fused_bn: the
+        # BatchNorm2d + ReLU pairs behind them through bn_train (the widths ROUTED_BN names), inert without fused_train
+        self.fused_train = bool(_get(model_cfg, "FUSED_TRAIN", False))
+        self.fused_bn = bool(_get(model_cfg, "FUSED_BN", False))
 
     def label_tables(self):
         """int array [label 0..C][head]: the class inside the head that a box of that label gets, or -1 when the head
@@ -634,6 +647,8 @@ class CenterHead(nn.Module):
     def forward(self, data_dict):
         if self.fused_convs and head_conv.applies(self, data_dict["spatial_features_2d"]):
             pred_dicts = head_conv.forward(self, data_dict["spatial_features_2d"])
+        elif self.fused_train and head_conv_train.applies(self, data_dict["spatial_features_2d"]):
+            pred_dicts = head_conv_train.forward_train(self, data_dict["spatial_features_2d"])
         else:
             x = self.shared_conv(data_dict["spatial_features_2d"])
             pred_dicts = [head(x) for head in self.heads_list]

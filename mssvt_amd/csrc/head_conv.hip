@@ -17,7 +17,10 @@
 //                                                 for sample b', map c, cell r.
 // The trunk and the finals are packed one branch (slice) per call.  (Reading a small slice's nine taps into LDS once instead
 // of streaming them was measured on the finals at 470 x 470: 2 % slower, so there is one form.)
+// The second half of the file is the TRAINING path of the shared layer and the trunk (forward without BatchNorm / ReLU, input,
+// weight and bias gradients): see the comment at its head.
 #include "split_conv.hip.h"
+#include "split_wgrad.hip.h"
 
 #define HC_MAX_SLICES 64
 
@@ -136,4 +139,272 @@ extern "C" int mssvt_head_conv_finals(const float *x, int B, int H, int W, int s
     if (!hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
     if (s == 32) return hc_launch<32, 16, BC_PLANAR>(x, nb * 32, 32, B, H, W, packed, nb, exp_in, nb, 0, y, nullptr, stream);
     return hc_launch<64, 16, BC_PLANAR>(x, nb * 64, 64, B, H, W, packed, nb, exp_in, nb, 0, y, nullptr, stream);
+}
+
+// ---- training: the shared layer and the trunk without BatchNorm / ReLU, forward and backward ---------------------------------------
+// (ref center_head.py :76-84 and :11-46 in training mode: Conv2d 3x3 (+ bias) whose BatchNorm2d + ReLU stay modules.)
+//   shared  y = conv(x, W) + bias: the inference kernel with scale 1, shift = bias, no ReLU, plain rows (BC_ROWS);
+//           dX = the convolution S -> Cin over dY with the taps rotated and the channel axes swapped (k_split_pack mode 4),
+//           Cin / 128 slices of 128 columns (64: one of 64); dW = k_split_wgrad on S x S tiles, rows = S, cols = Cin;
+//   trunk   t_b = conv(y, W_b) + bias_b for all nb branches in one launch, written BRANCH-MAJOR [nb][B H W][S] (BC_BRANCH);
+//           dy = sum_b rot(W_b) dT_b in one launch with one chain per element (BC_MULTI) from nb separate dT_b tensors;
+//           dW [nb][S][S][3][3] = k_split_wgrad with rows = nb S, row tile b on dT_b and its own words (MULTI);
+//   bias    db [nb][S] = the column sums of dT_b: pieces of HC_DB_PIECE rows per workgroup, each thread its rows in row order,
+//           the threads of a column in order, the pieces in piece order (no atomics).
+#define HC_SLICE_PIXELS 2048  // pixels per slice of the weight gradient: 108 slices at 470 x 470 (512 x 64: 127 MB of slabs)
+#define HC_DB_PIECE 2048      // rows per piece of the bias gradient
+#define HC_DB_THREADS 256
+
+extern "C" int mssvt_head_conv_train_supported(int cin, int s, int nb) {
+    return hc_cin(cin) && hc_s(s) && nb >= 1 && nb <= HC_MAX_SLICES ? 1 : 0;
+}
+// (cin, s) of the shared layer, or (s, s): the trunk
+extern "C" int mssvt_head_conv_train_wgrad_slice_pixels(int cin, int s) { return (hc_cin(cin) || cin == s) && hc_s(s) ? HC_SLICE_PIXELS : 0; }
+extern "C" int mssvt_head_conv_train_bias_piece_rows(int s) { return hc_s(s) ? HC_DB_PIECE : 0; }
+
+static bool hc_bad_size(int B, int H, int W, int a, int b) { return B <= 0 || H <= 0 || W <= 0 || a <= 0 || b <= 0; }
+// a host array of n device pointers: all present and 16-byte aligned
+static bool hc_bad_ptrs(const float *const *p, int n) {
+    if (!p) return true;
+    for (int i = 0; i < n; ++i)
+        if (!p[i] || bc_misaligned(p[i])) return true;
+    return false;
+}
+static bc_ptrs hc_ptrs(const float *const *p, int n) {
+    bc_ptrs out;
+    for (int i = 0; i < BC_MAX_BRANCHES; ++i) out.p[i] = i < n ? p[i] : nullptr;
+    return out;
+}
+static long long hc_slices(long long M) { return (M + HC_SLICE_PIXELS - 1) / HC_SLICE_PIXELS; }
+
+// x (B, H, W, cin) -> y (B, H, W, s) = conv + shift (the blob of mssvt_head_conv_shared_pack with the BatchNorm pointers NULL);
+// exp_workspace (B H W) int32 written here
+extern "C" int mssvt_head_conv_shared_train(const float *x, int B, int H, int W, int cin, int s, const void *packed,
+                                            int *exp_workspace, float *y, void *stream) {
+    if (!x || !packed || !exp_workspace || !y || hc_bad_size(B, H, W, cin, s) || bc_misaligned(x) || bc_misaligned(y) ||
+        bc_misaligned(packed))
+        return MSSVT_E_BADARG;
+    if (!hc_cin(cin) || !hc_s(s) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    int status = hc_expmap(x, (long long)B * H * W, cin, exp_workspace, (hipStream_t)stream);
+    if (status != MSSVT_OK) return status;
+#define HC_GO(CI, S) \
+    if (cin == CI && s == S) return hc_launch<CI, S, BC_ROWS>(x, CI, 0, B, H, W, packed, 1, exp_workspace, 1, 0, y, nullptr, stream);
+    HC_GO(64, 32) HC_GO(64, 64) HC_GO(256, 32) HC_GO(256, 64) HC_GO(384, 32) HC_GO(384, 64) HC_GO(512, 32) HC_GO(512, 64)
+#undef HC_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// [words of dy: B H W int32, padded to 256 bytes][the blob of the convolution s -> cin: 64 bytes, scale, shift, 9 s cin weights]
+extern "C" long long mssvt_head_conv_shared_dgrad_workspace_bytes(int B, int H, int W, int cin, int s) {
+    if (hc_bad_size(B, H, W, cin, s) || !hc_cin(cin) || !hc_s(s) || bc_too_many_pixels(B, H, W)) return 0;
+    return bw_round256(4ll * B * H * W) + BC_HDR(1) + 8ll * cin + 36ll * cin * s;
+}
+
+// dy (B, H, W, s), weight (s, cin, 3, 3) as Conv2d holds it -> dx (B, H, W, cin)
+extern "C" int mssvt_head_conv_shared_dgrad(const float *dy, const float *weight, int B, int H, int W, int cin, int s, float *dx,
+                                            void *workspace, void *stream) {
+    if (!dy || !weight || !dx || !workspace || hc_bad_size(B, H, W, cin, s) || bc_misaligned(dy) || bc_misaligned(weight) ||
+        bc_misaligned(dx) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!hc_cin(cin) || !hc_s(s) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W;
+    int *edy = reinterpret_cast<int *>(workspace);
+    void *blob = edy + bw_round256(4 * M) / 4;
+    const int ns = cin < 128 ? cin : 128;
+    int status = bc_pack(weight, 4, nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 3, s, cin, 0, ns, cin / ns, 0, 1, blob, st);
+    if (status != MSSVT_OK) return status;
+    status = hc_expmap(dy, M, s, edy, st);
+    if (status != MSSVT_OK) return status;
+#define HC_GO(S, NS)                                                                                                              \
+    if (s == S && ns == NS)                                                                                                       \
+        return bc_launch<S, NS, 3, false, BC_ROWS>(dy, S, 0, H, W, H, W, (int)M, blob, cin / NS, 3, 1, 1, edy, 1, 0, dx, nullptr, 0, \
+                                                   0, st);
+    HC_GO(32, 64) HC_GO(64, 64) HC_GO(32, 128) HC_GO(64, 128)
+#undef HC_GO
+    return MSSVT_E_TOOLARGE;
+}
+
+// [words of x: B H W int32, padded to 256 bytes][words of dy: the same][slices x 9 slabs of (s, cin) f32]
+extern "C" long long mssvt_head_conv_shared_wgrad_workspace_bytes(int B, int H, int W, int cin, int s) {
+    if (hc_bad_size(B, H, W, cin, s) || !hc_cin(cin) || !hc_s(s) || bc_too_many_pixels(B, H, W)) return 0;
+    const long long M = (long long)B * H * W;
+    return 2 * bw_round256(4 * M) + hc_slices(M) * 9 * cin * s * 4;
+}
+
+// x (B, H, W, cin), dy (B, H, W, s) -> dw (s, cin, 3, 3)
+extern "C" int mssvt_head_conv_shared_wgrad(const float *x, const float *dy, int B, int H, int W, int cin, int s, float *dw,
+                                            void *workspace, void *stream) {
+    if (!x || !dy || !dw || !workspace || hc_bad_size(B, H, W, cin, s) || bc_misaligned(x) || bc_misaligned(dy) ||
+        bc_misaligned(dw) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!hc_cin(cin) || !hc_s(s) || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W;
+    int *ex = reinterpret_cast<int *>(workspace), *edy = ex + bw_round256(4 * M) / 4;
+    float *slab = reinterpret_cast<float *>(edy + bw_round256(4 * M) / 4);
+    int status = hc_expmap(x, M, cin, ex, st);
+    if (status != MSSVT_OK) return status;
+    status = hc_expmap(dy, M, s, edy, st);
+    if (status != MSSVT_OK) return status;
+    // bw_launch(tapped, plain, .., cols, rows, ..): rows = s (dy, the plain operand), columns = cin (x, read at the tap's pixel)
+    if (s == 32) return bw_launch<32, BW_TAPS3>(x, dy, H, W, (int)M, cin, s, 1, 9, HC_SLICE_PIXELS, ex, edy, slab, dw, st);
+    return bw_launch<64, BW_TAPS3>(x, dy, H, W, (int)M, cin, s, 1, 9, HC_SLICE_PIXELS, ex, edy, slab, dw, st);
+}
+
+// ---- the bias gradient -----------------------------------------------------------------------------------------------------
+// part [branch][piece][S]: thread (g, l) adds the float4 column l of rows g, g + G, .. of the piece in row order, then the G
+// threads of a column are added in order of g
+template <int S>
+__global__ void __launch_bounds__(HC_DB_THREADS) k_hc_db_pieces(bc_ptrs dys, long long M, int pieces, float *part) {
+    constexpr int LPR = S / 4, G = HC_DB_THREADS / LPR;
+    __shared__ float4 sh[G][LPR];
+    const int l = threadIdx.x % LPR, g = threadIdx.x / LPR, piece = blockIdx.x, br = blockIdx.y;
+    const long long row0 = (long long)piece * HC_DB_PIECE;
+    const int nrows = (int)min((long long)HC_DB_PIECE, M - row0);
+    const float *base = dys.p[br] + row0 * S + 4 * l;
+    float4 a = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int r = g; r < nrows; r += G) {
+        const float4 v = *reinterpret_cast<const float4 *>(base + (long long)r * S);
+        a.x += v.x; a.y += v.y; a.z += v.z; a.w += v.w;
+    }
+    sh[g][l] = a;
+    __syncthreads();
+    if (threadIdx.x < S) {
+        const float *f = reinterpret_cast<const float *>(sh);
+        float t = f[threadIdx.x];
+        for (int j = 1; j < G; ++j) t += f[j * S + threadIdx.x];
+        part[((size_t)br * pieces + piece) * S + threadIdx.x] = t;
+    }
+}
+
+// db [branch][S]: the pieces in piece order; grid (nb), S threads
+static __global__ void __launch_bounds__(64) k_hc_db_sum(const float *part, int pieces, int S, float *db) {
+    const float *p = part + (size_t)blockIdx.x * pieces * S + threadIdx.x;
+    float t = p[0];
+    for (int i = 1; i < pieces; ++i) t += p[(size_t)i * S];
+    db[blockIdx.x * S + threadIdx.x] = t;
+}
+
+// [nb x pieces x s f32]
+extern "C" long long mssvt_head_conv_bgrad_workspace_bytes(int B, int H, int W, int s, int nb) {
+    if (hc_bad_size(B, H, W, s, nb) || !hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return 0;
+    return ((long long)B * H * W + HC_DB_PIECE - 1) / HC_DB_PIECE * nb * s * 4;
+}
+
+// host_dys: HOST array of nb device pointers, dT_b (B, H, W, s) each -> db [nb][s] (the shared layer: nb = 1)
+extern "C" int mssvt_head_conv_bgrad(const float *const *host_dys, int B, int H, int W, int s, int nb, float *db, void *workspace,
+                                     void *stream) {
+    if (!db || !workspace || hc_bad_size(B, H, W, s, nb) || bc_misaligned(db) || bc_misaligned(workspace)) return MSSVT_E_BADARG;
+    if (!hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    if (hc_bad_ptrs(host_dys, nb)) return MSSVT_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W;
+    const int pieces = (int)((M + HC_DB_PIECE - 1) / HC_DB_PIECE);
+    float *part = reinterpret_cast<float *>(workspace);
+    if (s == 32) k_hc_db_pieces<32><<<dim3(pieces, nb), HC_DB_THREADS, 0, st>>>(hc_ptrs(host_dys, nb), M, pieces, part);
+    else k_hc_db_pieces<64><<<dim3(pieces, nb), HC_DB_THREADS, 0, st>>>(hc_ptrs(host_dys, nb), M, pieces, part);
+    int status = mssvt_launch_status();
+    if (status != MSSVT_OK) return status;
+    k_hc_db_sum<<<nb, s, 0, st>>>(part, pieces, s, db);
+    return mssvt_launch_status();
+}
+
+// ---- the trunk ---------------------------------------------------------------------------------------------------------------
+// y (B, H, W, s) -> t [nb][B H W][s] = conv_b + shift_b (the blob of mssvt_head_conv_trunk_pack with the BatchNorm pointers
+// NULL); exp_workspace (B H W) int32 written here
+extern "C" int mssvt_head_conv_trunk_train(const float *y, int B, int H, int W, int s, int nb, const void *packed,
+                                           int *exp_workspace, float *t, void *stream) {
+    if (!y || !packed || !exp_workspace || !t || hc_bad_size(B, H, W, s, nb) || bc_misaligned(y) || bc_misaligned(t) ||
+        bc_misaligned(packed))
+        return MSSVT_E_BADARG;
+    if (!hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    int status = hc_expmap(y, (long long)B * H * W, s, exp_workspace, (hipStream_t)stream);
+    if (status != MSSVT_OK) return status;
+    if (s == 32) return hc_launch<32, 32, BC_BRANCH>(y, 32, 0, B, H, W, packed, nb, exp_workspace, 1, 0, t, nullptr, stream);
+    return hc_launch<64, 64, BC_BRANCH>(y, 64, 0, B, H, W, packed, nb, exp_workspace, 1, 0, t, nullptr, stream);
+}
+
+// the power of two of ALL branches' weights (one accumulation chain reads them all) -> header record 0, scale 1, shift 0
+static __global__ void __launch_bounds__(1024) k_hc_prep_multi(bc_ptrs w, int nb, int count, int ns, unsigned char *blob) {
+    __shared__ int part[16];
+    int m = 0;
+    for (int b = 0; b < nb; ++b)
+        for (int i = threadIdx.x; i < count; i += blockDim.x) m = max(m, bc_abs_bits(w.p[b][i]));
+    for (int off = 32; off; off >>= 1) m = max(m, __shfl_xor(m, off));
+    if (lane_id() == 0) part[threadIdx.x / MSSVT_WAVE] = m;
+    __syncthreads();
+    if (threadIdx.x < 16) {
+        m = 0;
+        for (int i = 0; i < 16; ++i) m = max(m, part[i]);
+        int eb;
+        const bool norm = pow2_norm_exponent(m, eb);
+        const int word[2] = {norm ? 0x7F000000 - eb : 0x3F800000, norm ? eb : 0x3F800000};
+        reinterpret_cast<int *>(blob)[threadIdx.x] = threadIdx.x < 2 ? word[threadIdx.x] : 0;
+    }
+    float *scale = reinterpret_cast<float *>(blob + BC_HDR(1));
+    for (int c = threadIdx.x; c < ns; c += blockDim.x) {
+        scale[c] = 1.f;
+        scale[ns + c] = 0.f;
+    }
+}
+
+// [words of the dT_b: nb B H W int32, padded to 256 bytes][the blob of the convolution nb s -> s]
+extern "C" long long mssvt_head_conv_trunk_dgrad_workspace_bytes(int B, int H, int W, int s, int nb) {
+    if (hc_bad_size(B, H, W, s, nb) || !hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return 0;
+    return bw_round256(4ll * nb * B * H * W) + BC_HDR(1) + 8ll * s + 36ll * s * s * nb;
+}
+
+// host_dts / host_weights: HOST arrays of nb device pointers, dT_b (B, H, W, s) and W_b (s, s, 3, 3) -> dy (B, H, W, s)
+extern "C" int mssvt_head_conv_trunk_dgrad(const float *const *host_dts, const float *const *host_weights, int B, int H, int W,
+                                           int s, int nb, float *dy, void *workspace, void *stream) {
+    if (!dy || !workspace || hc_bad_size(B, H, W, s, nb) || bc_misaligned(dy) || bc_misaligned(workspace)) return MSSVT_E_BADARG;
+    if (!hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    if (hc_bad_ptrs(host_dts, nb) || hc_bad_ptrs(host_weights, nb)) return MSSVT_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W;
+    int *edt = reinterpret_cast<int *>(workspace);
+    unsigned char *blob = reinterpret_cast<unsigned char *>(edt + bw_round256(4 * nb * M) / 4);
+    k_hc_prep_multi<<<1, 1024, 0, st>>>(hc_ptrs(host_weights, nb), nb, 9 * s * s, s, blob);
+    int status = mssvt_launch_status();
+    for (int b = 0; b < nb && status == MSSVT_OK; ++b) {
+        k_split_pack<<<divup(9ll * s * s / 8, 256), 256, 0, st>>>(host_weights[b], 4, 3, s, s, s, 1, 0, 1, BC_HDR(1), blob, nb, b);
+        status = mssvt_launch_status();
+        if (status == MSSVT_OK) status = hc_expmap(host_dts[b], M, s, edt + (size_t)b * M, st);
+    }
+    if (status != MSSVT_OK) return status;
+    if (s == 32)
+        return bc_launch<32, 32, 3, false, BC_MULTI>(nullptr, 32, nb, H, W, H, W, (int)M, blob, 1, 3, 1, 1, edt, 1, 0, dy, nullptr, 0, 0,
+                                                     st, hc_ptrs(host_dts, nb));
+    return bc_launch<64, 64, 3, false, BC_MULTI>(nullptr, 64, nb, H, W, H, W, (int)M, blob, 1, 3, 1, 1, edt, 1, 0, dy, nullptr, 0, 0, st,
+                                                 hc_ptrs(host_dts, nb));
+}
+
+// [words of y: B H W int32, padded to 256 bytes][words of the dT_b: nb B H W, padded][slices x 9 slabs of (nb s, s) f32]
+extern "C" long long mssvt_head_conv_trunk_wgrad_workspace_bytes(int B, int H, int W, int s, int nb) {
+    if (hc_bad_size(B, H, W, s, nb) || !hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return 0;
+    const long long M = (long long)B * H * W;
+    return bw_round256(4 * M) + bw_round256(4 * nb * M) + hc_slices(M) * 9 * nb * s * s * 4;
+}
+
+// y (B, H, W, s), host_dts: HOST array of nb device pointers dT_b (B, H, W, s) -> dw [nb][s][s][3][3]
+extern "C" int mssvt_head_conv_trunk_wgrad(const float *y, const float *const *host_dts, int B, int H, int W, int s, int nb,
+                                           float *dw, void *workspace, void *stream) {
+    if (!y || !dw || !workspace || hc_bad_size(B, H, W, s, nb) || bc_misaligned(y) || bc_misaligned(dw) || bc_misaligned(workspace))
+        return MSSVT_E_BADARG;
+    if (!hc_s(s) || nb > HC_MAX_SLICES || bc_too_many_pixels(B, H, W)) return MSSVT_E_TOOLARGE;
+    if (hc_bad_ptrs(host_dts, nb)) return MSSVT_E_BADARG;
+    hipStream_t st = (hipStream_t)stream;
+    const long long M = (long long)B * H * W;
+    int *ey = reinterpret_cast<int *>(workspace), *edt = ey + bw_round256(4 * M) / 4;
+    float *slab = reinterpret_cast<float *>(edt + bw_round256(4 * nb * M) / 4);
+    int status = hc_expmap(y, M, s, ey, st);
+    for (int b = 0; b < nb && status == MSSVT_OK; ++b) status = hc_expmap(host_dts[b], M, s, edt + (size_t)b * M, st);
+    if (status != MSSVT_OK) return status;
+    // rows = nb s: row tile b is branch b (its own tensor and words), columns = s (y, read at the tap's pixel)
+    if (s == 32)
+        return bw_launch<32, BW_TAPS3, true>(y, nullptr, H, W, (int)M, s, nb * s, 1, 9, HC_SLICE_PIXELS, ey, edt, slab, dw, st, 0, 0,
+                                             hc_ptrs(host_dts, nb));
+    return bw_launch<64, BW_TAPS3, true>(y, nullptr, H, W, (int)M, s, nb * s, 1, 9, HC_SLICE_PIXELS, ey, edt, slab, dw, st, 0, 0,
+                                         hc_ptrs(host_dts, nb));
 }

@@ -78,7 +78,21 @@ struct bc_geom {
     static constexpr size_t LDS = 2 * (size_t)2 * IMG * 16;  // two buffers of a hi and a lo image
 };
 
-enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2, BC_DOWN2 };
+enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2, BC_DOWN2, BC_BRANCH, BC_MULTI };
+#define BC_MAX_BRANCHES 64
+// the extra (last) argument of the kernel: nothing, but for BC_MULTI the base pointers of its input tensors, by value
+struct bc_ptrs {
+    const float *p[BC_MAX_BRANCHES];
+};
+struct bc_none {};
+template <int OUT>
+struct bc_extra {
+    typedef bc_none type;
+};
+template <>
+struct bc_extra<BC_MULTI> {
+    typedef bc_ptrs type;
+};
 // OUT: y (M, nsl NS) rows; rows and eout [pixel][nsl], the largest |y| of the pixel's slice as bits; slice sl's k <= 16 maps
 // planar at float kbase B H W; rows of `ystride` floats of which the layer owns channels [ybase, ybase + nsl NS) (a slice of a
 // wider tensor; ystride % 4 == ybase % 4 == 0 keeps the stores aligned); UP2: the four phases of a 2 x 2 stride-2 transposed
@@ -95,19 +109,36 @@ enum { BC_ROWS, BC_ROWS_WORDS, BC_PLANAR, BC_ROWS_INTO, BC_UP2, BC_DOWN2 };
 // phase grid is Ho_ / 2 (py = 1) or H (py = 0) rows by Wo_ / 2 or W columns: an empty phase (Ho_ = 1 or Wo_ = 1) and the blocks
 // beyond a smaller phase leave at once; the 4-tap phase is dealt first.  The blob holds the layer's 9 taps in phase order
 // (k_split_pack, transposed = 3) under one header record; ksize_, stride_ and dil_ are not read.
+// BRANCH: rows as BC_ROWS, but slice-major: y is [nsl][M][NS], every slice a dense (M, NS) matrix.
+// MULTI: y (M, NS) rows = the SUM over `gin` input tensors (the argument counts them in this form; SLICED is false) of their
+// convolutions, as ONE convolution of gin CIN input channels: the stage loop runs over (tap, tensor) -- the "chunk" of a stage
+// is the tensor, its rows come from that tensor's own base pointer (the kernel's last argument; x is not read), CIN <= 128 is
+// one chunk.  emap is [tensor][pixel]; an output pixel's power of two is the largest over its receptive field AND all tensors
+// (one accumulation chain per element).  The blob holds one block per (tap, tensor) under one header record.
 
 // TAPS 0: ksize x ksize taps (3: padding = dil, 1: none) at `stride` / `dil`, output Ho x Wo;  TAPS 3: 3 x 3, stride 1,
 // dilation 1, Ho = H, Wo = W as constants (those five arguments are not read).
 // SLICED false: pixels of CIN floats, one exponent word per pixel, every slice under header record 0;  true: pixels of
 // `xstride` floats of which slice sl reads channels [sl gin, sl gin + CIN), emap [pixel][egroups] of which it reads word sl
 // when egroups > 1 (else word 0), and header record sl.
+template <int CIN, int NS, int OUT>
+__device__ __forceinline__ int bc_chunks(int, bc_none) { return bc_geom<CIN, NS>::CHUNKS; }
+template <int CIN, int NS, int OUT>
+__device__ __forceinline__ int bc_chunks(int gin, const bc_ptrs &) { return gin; }
+// the rows of chunk `chunk`: x itself, or the chunk's own tensor
+__device__ __forceinline__ const float *bc_rows(const float *x, int, bc_none) { return x; }
+__device__ __forceinline__ const float *bc_rows(const float *, int chunk, const bc_ptrs &in) { return in.p[chunk]; }
+
 template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
 __global__ void __launch_bounds__(BC_THREADS, 1)
     k_split_conv(const float *x, int xstride_, int gin, int H, int W, int Ho_, int Wo_, int M_, const unsigned char *blob, int nsl,
                  int ksize_, int stride_, int dil_, const int *emap, int egroups_, int relu, float *y, int *eout, int ystride,
-                 int ybase) {
+                 int ybase, typename bc_extra<OUT>::type inputs) {
     using G = bc_geom<CIN, NS>;
-    constexpr int KC = G::KC, KS = G::KS, NT = G::NT, CHUNKS = G::CHUNKS, IMG = G::IMG;
+    constexpr int KC = G::KC, KS = G::KS, NT = G::NT, IMG = G::IMG;
+    constexpr bool MULTI = OUT == BC_MULTI;
+    static_assert(!MULTI || (G::CHUNKS == 1 && !SLICED), "BC_MULTI: one chunk per input tensor");
+    const int CHUNKS = bc_chunks<CIN, NS, OUT>(gin, inputs);  // (a constant in every form but MULTI)
     constexpr int FR = (2 * IMG + BC_THREADS - 1) / BC_THREADS;  // fragments of a block per thread ...
     constexpr int FP = (FR + KS - 1) / KS;  // ... of which a thread moves at most FP under each k step of the previous block
     extern __shared__ float4 bc_lds[];
@@ -159,7 +190,12 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
             for (int ky = 0; ky < ksy; ++ky)
                 for (int kx = 0; kx < ksx; ++kx) {
                     const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
-                    if (iy >= 0 && iy < H && ix >= 0 && ix < W) e = max(e, emap[(size_t)(img[j] + iy * W + ix) * egroups + eoff]);
+                    if (!(iy >= 0 && iy < H && ix >= 0 && ix < W)) continue;
+                    if (MULTI) {
+                        for (int c = 0; c < CHUNKS; ++c) e = max(e, emap[(size_t)c * M_ + img[j] + iy * W + ix]);
+                    } else {
+                        e = max(e, emap[(size_t)(img[j] + iy * W + ix) * egroups + eoff]);
+                    }
                 }
         float s_un;
         pow2_norm(__builtin_bit_cast(float, e), s_in[j], s_un);  // (the word's exponent alone counts: a NaN passes through)
@@ -180,7 +216,8 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
             const int iy = oy0[j] + ky * dil, ix = ox0[j] + kx * dil;
             xa[j][0] = xa[j][1] = make_float4(0.f, 0.f, 0.f, 0.f);
             if (live[j] && iy >= 0 && iy < H && ix >= 0 && ix < W) {
-                const float *p = x + (size_t)(img[j] + iy * W + ix) * xstride + cbase + chunk * KC + 32 * P + 8 * g;
+                const float *p = bc_rows(x, chunk, inputs) + (size_t)(img[j] + iy * W + ix) * xstride + cbase +
+                                 (MULTI ? 0 : chunk * KC) + 32 * P + 8 * g;
                 xa[j][0] = *reinterpret_cast<const float4 *>(p);
                 xa[j][1] = *reinterpret_cast<const float4 *>(p + 4);
             }
@@ -270,7 +307,8 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
             } else if (OUT == BC_ROWS_INTO || OUT == BC_UP2 || DN) {
                 *reinterpret_cast<float4 *>(y + row + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
             } else {
-                *reinterpret_cast<float4 *>(y + (size_t)mc * cout + sl * NS + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
+                const size_t at = OUT == BC_BRANCH ? ((size_t)sl * M + mc) * NS : (size_t)mc * cout + sl * NS;
+                *reinterpret_cast<float4 *>(y + at + 16 * t + 4 * g) = make_float4(o[0], o[1], o[2], o[3]);
             }
         }
         if (OUT == BC_ROWS_WORDS) {
@@ -284,7 +322,7 @@ __global__ void __launch_bounds__(BC_THREADS, 1)
 template <int CIN, int NS, int TAPS, bool SLICED, int OUT>
 static int bc_launch(const float *x, int xstride, int gin, int H, int W, int Ho, int Wo, int M, const void *packed, int nsl,
                      int ksize, int stride, int dil, const int *emap, int egroups, int relu, float *y, int *eout, int ystride, int ybase,
-                     hipStream_t st) {
+                     hipStream_t st, typename bc_extra<OUT>::type inputs = {}) {
     const auto kernel = k_split_conv<CIN, NS, TAPS, SLICED, OUT>;
     constexpr size_t LDS = bc_geom<CIN, NS>::LDS;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
@@ -292,7 +330,7 @@ static int bc_launch(const float *x, int xstride, int gin, int H, int W, int Ho,
     const int nblocks = divup(M, BC_BLOCK_PIXELS);
     const dim3 grid = OUT == BC_UP2 ? dim3((nblocks + 7) / 8 * 8 * nsl) : dim3(nblocks, nsl, OUT == BC_DOWN2 ? 4 : 1);
     kernel<<<grid, BC_THREADS, LDS, st>>>(x, xstride, gin, H, W, Ho, Wo, M, reinterpret_cast<const unsigned char *>(packed), nsl,
-                                          ksize, stride, dil, emap, egroups, relu, y, eout, ystride, ybase);
+                                          ksize, stride, dil, emap, egroups, relu, y, eout, ystride, ybase, inputs);
     return mssvt_launch_status();
 }
 
@@ -341,9 +379,14 @@ static __global__ void __launch_bounds__(1024) k_split_prep(const float *w, long
 // (cin, k, 1, 1); 2 (ksize = 1): (cin, k / 4, 2, 2), column n = phase (dy 2 + dx) k / 4 + output channel (the UP2 form);
 // 3 (ksize = 3): the Conv2d weight (cin, k, 3, 3) of the layer whose INPUT gradient the blob computes (the DOWN2 form) -- the
 // channel axes swap and stage tap s is tap (ky, kx) of the tensor in phase order: (2,2) (2,0) (0,2) (0,0) | (2,1) (0,1) |
-// (1,2) (1,0) | (1,1), the dY offset (0 or 1) of a tap being its place in its phase's list
+// (1,2) (1,0) | (1,1), the dY offset (0 or 1) of a tap being its place in its phase's list;
+// 4 (ksize = 3): the same tensor for the input gradient of the layer at STRIDE 1 -- the channel axes swap and stage tap t is
+// tap 8 - t of the tensor (the taps rotated by 180 degrees).
+// A slice holds nstages sstride blocks of which this call writes blocks st sstride + soff (sstride = 1, soff = 0: all of them;
+// BC_MULTI: sstride input tensors, this one is soff)
 static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int transposed, int ksize, int cin, int k, int ns,
-                                                           int nsl, int sl, int n_slices, int hdr, unsigned char *blob) {
+                                                           int nsl, int sl, int n_slices, int hdr, unsigned char *blob, int sstride,
+                                                           int soff) {
     const int KC = BC_KC(cin), KS = KC / 32, NT = ns / 16, CHUNKS = cin / KC, IMG = KS * NT * 64;
     const int ntaps = ksize * ksize, nstages = ntaps * CHUNKS;
     const long long total = (long long)n_slices * nstages * IMG, id = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -357,6 +400,7 @@ static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int t
 #pragma unroll
     for (int i = 0; i < 8; ++i)
         v[i] = n >= k              ? 0.f
+               : transposed == 4 ? w[((size_t)(c0 + i) * k + n) * 9 + 8 - tap]
                : transposed == 3 ? w[((size_t)(c0 + i) * k + n) * 9 + (int)((0x435170268ull >> (4 * tap)) & 15)]
                : transposed == 2 ? w[((size_t)(c0 + i) * (k / 4) + n % (k / 4)) * 4 + n / (k / 4)]
                : transposed      ? w[(size_t)(c0 + i) * k + n]
@@ -364,7 +408,7 @@ static __global__ void __launch_bounds__(256) k_split_pack(const float *w, int t
     h16x8 h, l;
     split8_scaled_rne(make_float4(v[0], v[1], v[2], v[3]), make_float4(v[4], v[5], v[6], v[7]), w_in, h, l);
     h16x8 *blk = reinterpret_cast<h16x8 *>(blob + hdr + (size_t)nsl * ns * 8) +
-                    ((size_t)(sl + slice) * nstages + st) * 2 * IMG;
+                    (((size_t)(sl + slice) * nstages + st) * sstride + soff) * 2 * IMG;
     blk[f] = h;
     blk[IMG + f] = l;
 }
@@ -384,6 +428,6 @@ static int bc_pack(const float *w, int transposed, const float *bias, const floa
     int status = mssvt_launch_status();
     if (status != MSSVT_OK) return status;
     k_split_pack<<<divup((long long)n_slices * ksize * ksize * cin * ns / 8, 256), 256, 0, st>>>(w, transposed, ksize, cin, k, ns,
-                                                                                                 nsl, sl, n_slices, hdr, blob);
+                                                                                                 nsl, sl, n_slices, hdr, blob, 1, 0);
     return mssvt_launch_status();
 }

@@ -70,16 +70,28 @@ struct bw_geom {
 };
 
 enum { BW_TAPS3, BW_PHASES, BW_DOWN };
+// MULTI: the plain operand is one tensor of C floats per pixel for every ROW TILE -- row tile b reads plain.p[b] and the words
+// eplain + b M, so the slice's power of two of the plain operand is that tensor's own (rows = tiles x C; plain_op is not read)
+template <bool MULTI>
+struct bw_extra {
+    typedef bc_none type;
+};
+template <>
+struct bw_extra<true> {
+    typedef bc_ptrs type;
+};
+__device__ __forceinline__ const float *bw_plain(const float *plain_op, int co0, int, bc_none) { return plain_op + co0; }
+__device__ __forceinline__ const float *bw_plain(const float *, int, int tile, const bc_ptrs &in) { return in.p[tile]; }
 // tapped_op: the TAPPED operand, pixels of `cols` floats (the tile's columns); plain_op: the PLAIN operand, M = B H W pixels of
 // `rows` floats (the tile's rows); etapped / eplain: their k_split_expmap words; slab [slice][tap][rows][cols].  H, W: the grid
 // of the reduction pixels; step: the dilation (BW_TAPS3) or the stride s (BW_PHASES: tapped_op then has s s M pixels); Ht, Wt:
 // the grid of the tapped operand (read by BW_DOWN alone: the other maps derive it from H, W and step).
 // BW_TAPS3, BW_DOWN: plain = dY, rows = cout, tapped = X, cols = cin;  BW_PHASES: plain = X, rows = cin, tapped = dY, cols = cout.
 // grid (slices, (rows / C) (cols / C), taps)
-template <int C, int MAP>
+template <int C, int MAP, bool MULTI = false>
 __global__ void __launch_bounds__(bw_geom<C>::THREADS)
     k_split_wgrad(const float *tapped_op, const float *plain_op, int H, int W, int M, int cols, int rows, int step, int slice,
-                  const int *etapped, const int *eplain, float *slab, int Ht, int Wt) {
+                  const int *etapped, const int *eplain_, float *slab, int Ht, int Wt, typename bw_extra<MULTI>::type plains) {
     using G = bw_geom<C>;
     constexpr int TM = G::TM, TN = G::TN, RS = G::RS, IMG = G::IMG, BUF = G::BUF, IT = G::IT, THREADS = G::THREADS;
     extern __shared__ __attribute__((aligned(16))) char bw_lds[];
@@ -90,6 +102,9 @@ __global__ void __launch_bounds__(bw_geom<C>::THREADS)
     const int oy = MAP == BW_TAPS3 ? (ky - 1) * step : MAP == BW_DOWN ? ky - 1 : ky;
     const int ox = MAP == BW_TAPS3 ? (kx - 1) * step : MAP == BW_DOWN ? kx - 1 : kx;
     const int HW = H * W;
+    const float *plain = bw_plain(plain_op, co0, co0 / C, plains);  // the first float of the tile's rows at pixel 0
+    const int ppitch = MULTI ? C : rows;
+    const int *eplain = MULTI ? eplain_ + (size_t)(co0 / C) * M : eplain_;
     const int m0 = s * slice, m1 = M - m0 > slice ? m0 + slice : M;  // the slice's pixels [m0, m1): may span two samples
     // the pixel the tap reads for reduction pixel m, or -1 outside the image (a phase never leaves it: s^2 M < 2^31)
     auto tapped = [&](int m) {
@@ -139,7 +154,7 @@ __global__ void __launch_bounds__(bw_geom<C>::THREADS)
             dv[i][0] = dv[i][1] = xv[i][0] = xv[i][1] = make_float4(0.f, 0.f, 0.f, 0.f);
             const int q = m < m1 ? tapped(m) : -1;
             if (q >= 0) {
-                const float *pd = plain_op + (size_t)m * rows + co0 + 8 * ch;
+                const float *pd = plain + (size_t)m * ppitch + 8 * ch;
                 const float *pX = tapped_op + (size_t)q * cols + ci0 + 8 * ch;
                 dv[i][0] = *reinterpret_cast<const float4 *>(pd);
                 dv[i][1] = *reinterpret_cast<const float4 *>(pd + 4);
@@ -231,17 +246,17 @@ static __global__ void __launch_bounds__(256) k_split_wgrad_sum(const float *sla
 }
 
 // (the kernel's arguments; dw is (rows, cols, taps))
-template <int C, int MAP>
+template <int C, int MAP, bool MULTI = false>
 static int bw_launch(const float *tapped_op, const float *plain_op, int H, int W, int M, int cols, int rows, int step, int ntaps,
                      int slice, const int *etapped, const int *eplain, float *slab, float *dw, hipStream_t st, int Ht = 0,
-                     int Wt = 0) {
+                     int Wt = 0, typename bw_extra<MULTI>::type plains = {}) {
     using G = bw_geom<C>;
-    const auto kernel = k_split_wgrad<C, MAP>;
+    const auto kernel = k_split_wgrad<C, MAP, MULTI>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)G::LDS);
     if (e != hipSuccess) return (int)e;
     const int nslices = divup(M, slice);
     kernel<<<dim3(nslices, (rows / C) * (cols / C), ntaps), G::THREADS, G::LDS, st>>>(tapped_op, plain_op, H, W, M, cols, rows, step, slice,
-                                                                                   etapped, eplain, slab, Ht, Wt);
+                                                                                   etapped, eplain, slab, Ht, Wt, plains);
     int status = mssvt_launch_status();
     if (status != MSSVT_OK) return status;
     k_split_wgrad_sum<<<divup(ntaps * cols * rows, 256), 256, 0, st>>>(slab, nslices, cols, rows, ntaps, dw);
