@@ -515,6 +515,16 @@ __device__ __forceinline__ void ffw_weight_frags(const float *W1, const float *W
         ffw_split8(src, src + 16, W2h[ks], W2l[ks]);
     }
 }
+// The same in two steps for k_ffn_ws: the fp32 words of a fragment pair are LOADED into the registers of (hi, lo) -- one
+// 16-byte load each, as many loads as the packed form issues -- and split in place later
+__device__ __forceinline__ void ffw_raw8(const float *p0, const float *p1, h16x8 &hi, h16x8 &lo) {
+    hi = __builtin_bit_cast(h16x8, *reinterpret_cast<const float4 *>(p0));
+    lo = __builtin_bit_cast(h16x8, *reinterpret_cast<const float4 *>(p1));
+}
+__device__ __forceinline__ void ffw_split_raw8(h16x8 &hi, h16x8 &lo) {
+    const float4 v0 = __builtin_bit_cast(float4, hi), v1 = __builtin_bit_cast(float4, lo);
+    split8_rtz(f32x4{v0.x, v0.y, v0.z, v0.w}, f32x4{v1.x, v1.y, v1.z, v1.w}, hi, lo);
+}
 
 // the fragments of all waves, split once per parameter version: [wave][fragment][lane] x 16 bytes
 template <int C, int FF>
@@ -556,10 +566,12 @@ extern "C" int mssvt_debug_read_ffn_ws_spans(unsigned long long *host) {
 // STOREY = false (round 6): y itself has no reader -- the last Block in front of a CompressBlock, which takes only the
 // LayerNorm output (it has no input residual, ref mssvt_backbone.py:370-385) -- and is not stored: 4 C of the launch's 12 C
 // bytes per row
-template <int C, int FF, bool TABBED, bool NORM2, bool STOREY = true>
+// NDEV: the row count is read from the device (a.n_rows_dev, a.n_rows = capacity).  A template parameter because the ORDER
+// of the head's loads depends on it (below).
+template <int C, int FF, bool TABBED, bool NORM2, bool STOREY, bool NDEV>
 __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a, const h16x8 *packed) {
 #ifdef MSSVT_STAMPS
-    unsigned long long ws_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ws_t = __builtin_readcyclecounter();
+    unsigned long long ws_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, ws_t = __builtin_readcyclecounter(), ws_last = ws_t;
     int ws_tiles = 0;
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_ws_span[2 * blockIdx.x] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -574,27 +586,28 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
     const int lane = lane_id(), la = lane & 15, g = lane >> 4;
     const int wv = __builtin_amdgcn_readfirstlane(threadIdx.x / MSSVT_WAVE);
     const int r = wv * RPW + lane / LPR, q = lane % LPR;  // row-wise view: row of the tile, channels [4 q, 4 q + 4)
-    const int n = a.n_rows_dev ? *a.n_rows_dev : a.n_rows;
-    const int tiles = (n + 15) >> 4;
     // Tiles are dealt so that an XCD owns ONE contiguous eighth of the rows and its gridDim / 8 workgroups walk it side by side
     // (workgroups are dispatched round-robin over the XCDs: block b runs on XCD b % 8 -- observed, used for speed only): the
     // voxels of a window lie in three x-slabs ~160 rows apart in the (b, x, y, z) order and gather the SAME attention rows, so
     // the rows a workgroup gathers were mostly fetched into ITS XCD's L2 by a neighbour a moment ago.  Round-robin tiles put
     // consecutive tiles on different XCDs (each with an L2 of its own): 146 MB of HBM traffic per launch against 114 MB
     // algorithmic.
-    int tstep = gridDim.x, tend = tiles, tile0 = blockIdx.x;
-    if ((gridDim.x & 7) == 0 && tiles >= 8 * (int)gridDim.x) {
-        const int x = blockIdx.x & 7, per_xcd = (tiles + 7) >> 3;
-        tstep = gridDim.x >> 3;
-        tile0 = x * per_xcd + (int)(blockIdx.x >> 3);
-        tend = min((x + 1) * per_xcd, tiles);
+    int n = a.n_rows, tstep = gridDim.x, tend = 0, tile0 = blockIdx.x;
+#define FFW_DEAL()                                                                                          \
+    {                                                                                                       \
+        const int tiles_ = (n + 15) >> 4;                                                                   \
+        tend = tiles_;                                                                                      \
+        if ((gridDim.x & 7) == 0 && tiles_ >= 8 * (int)gridDim.x) {                                         \
+            const int x_ = blockIdx.x & 7, per_xcd_ = (tiles_ + 7) >> 3;                                    \
+            tstep = gridDim.x >> 3;                                                                         \
+            tile0 = x_ * per_xcd_ + (int)(blockIdx.x >> 3);                                                 \
+            tend = min((x_ + 1) * per_xcd_, tiles_);                                                        \
+        }                                                                                                   \
     }
-    if (n <= 0 || tile0 >= tend) return;
 
     // Rows past the end are CLAMPED to row n - 1 everywhere (table, gathers, stores): such lanes compute exactly what the
     // lanes of row n - 1 compute and store the same values to the same place -- no predication, hence no branches
     // inside the barrier intervals (the scheduler interleaves MFMA and VALU only within one basic block).
-    int tile = tile0;
     int4 tr = make_int4(0, 0, 0, 0);
     float4 tw = make_float4(0.f, 0.f, 0.f, 0.f);
     int own = 0;
@@ -703,52 +716,129 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
 #define FFW_U2(T_, i_) ffw_relu2(pk_fma(pk2(ul_[T_][i_], ul_[T_][i_ + 1]) + pk2(uk_[T_][i_], uk_[T_][i_ + 1]), pk1(SPLIT_INV), \
                                         pk2(um_[T_][i_], um_[T_][i_ + 1])))
 
-    // ---- the first tile's rows are requested before the weights (both pure latency) -------------------------
-    FFW_TAB(tile, tr, tw, own)
-    FFW_ISSUE(tile, tr, tw, own)
-    int4 trn = tr;
-    float4 twn = tw;
-    int ownn = own;
-    FFW_TAB(min(tile + tstep, tend - 1), trn, twn, ownn)
-
-    // ---- this wave's weight slices as A fragments: pre-split by k_ffn_pack, or split here ---------------------
+    // ---- head: the weight transfer starts with the first instructions and the first tile runs under it ----------------
+    // A CU reads 32 fragments per wave (256 KB at C = 128) that every other CU reads too, out of its XCD's L2: 3.5 - 4 us,
+    // the longest item of the head.  Vector loads return in issue order, so what is issued BEHIND fragments waits for them:
+    //   host row count:    LayerNorm parameters, table words of tile 0 | W1 | wait: table | gathers of tile 0, table words
+    //                      of the next tile, biases | W2
+    //   device row count:  the count (as a vector word: through the scalar cache it is waited for at once), LayerNorm
+    //                      parameters | W1 | wait: count | table words of tile 0 | wait | gathers ... as above
+    // (no address that depends on n is formed before n is known: with the count on the device the table words queue behind
+    // W1).  A(t0) needs the gathers and GEMM1(t0) needs W1 only; W2 travels under both and is first waited for by GEMM2 of
+    // the first tile.  The sched_barriers keep the groups in this order.
+    unsigned vz = 0;  // a zero the compiler cannot see through: block_attn.hip, KVH_WORD
+    int n_v = 0;
+    if (NDEV) {
+        asm volatile("" : "+v"(vz));
+        n_v = *reinterpret_cast<const int *>(reinterpret_cast<const char *>(a.n_rows_dev) + vz);
+    }
+    // row-wise constants of this lane's 4 channels: staged by wave 0
+    // (kept in LDS, not in 16 VGPRs: with the weights in 128 registers the loop sits at the 256-register limit, and every
+    // register less is a spill or a v_mov less; four ds_read_b128 per tile)
+    float4 lnv0, lnv1, lnv2, lnv3;
+    if (threadIdx.x < C / 4) {
+        const int c4 = threadIdx.x * 4;
+        lnv0 = *reinterpret_cast<const float4 *>(a.ln_w + c4);
+        lnv1 = *reinterpret_cast<const float4 *>(a.ln_b + c4);
+        if (NORM2) {
+            lnv2 = *reinterpret_cast<const float4 *>(a.ln2_w + c4);
+            lnv3 = *reinterpret_cast<const float4 *>(a.ln2_b + c4);
+        }
+        asm volatile("" ::: "memory");  // the loads stay HERE, in front of the fragments (they were sunk to the LDS stores)
+    }
+    int tile = 0;
+    if (!NDEV) {
+        FFW_DEAL()
+        if (n <= 0 || tile0 >= tend) return;
+        tile = tile0;
+        FFW_TAB(tile, tr, tw, own)
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // this wave's weight slices as A fragments: pre-split by k_ffn_pack, or fp32 words split below.  Both forms issue the SAME
+    // number of loads per group: where two paths with different counts join, every counted wait behind the join falls back to
+    // the shorter path's count (the table wait became vmcnt(2) behind 16 fragment loads)
     h16x8 W1h[2][NP], W1l[2][NP], W2h[NW], W2l[NW];
+    const size_t woff = (size_t)wv * (4 * NP + 2 * NW) * 64 + lane;
     if (packed) {
-        const h16x8 *src = packed + (size_t)wv * (4 * NP + 2 * NW) * 64 + lane;
+        const h16x8 *wsrc = packed + woff;
 #pragma unroll
         for (int T = 0; T < 2; ++T)
 #pragma unroll
             for (int P = 0; P < NP; ++P) {
-                W1h[T][P] = src[((T * NP + P) * 2) * 64];
-                W1l[T][P] = src[((T * NP + P) * 2 + 1) * 64];
+                W1h[T][P] = wsrc[((T * NP + P) * 2) * 64];
+                W1l[T][P] = wsrc[((T * NP + P) * 2 + 1) * 64];
             }
-#pragma unroll
-        for (int ks = 0; ks < NW; ++ks) {
-            W2h[ks] = src[(4 * NP + 2 * ks) * 64];
-            W2l[ks] = src[(4 * NP + 2 * ks + 1) * 64];
-        }
     } else {
-        ffw_weight_frags<C, FF>(a.W1, a.W2, wv, la, g, W1h, W1l, W2h, W2l);
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int P = 0; P < NP; ++P) {
+                const float *src = a.W1 + (size_t)(32 * wv + 16 * T + la) * C + 32 * P + 8 * g;
+                ffw_raw8(src, src + 4, W1h[T][P], W1l[T][P]);
+            }
     }
+    __builtin_amdgcn_sched_barrier(0);
+    if (NDEV) {
+        n = __builtin_amdgcn_readfirstlane(n_v);
+        FFW_DEAL()
+        if (n <= 0 || tile0 >= tend) return;
+        tile = tile0;
+        FFW_TAB(tile, tr, tw, own)
+    }
+    // (issued in front of W1 and back by now: stored here, their 16 registers are free again under the gathers and W2)
+    if (threadIdx.x < C / 4) {
+        const int c4 = threadIdx.x * 4;
+        *reinterpret_cast<float4 *>(lnp + c4) = lnv0;
+        *reinterpret_cast<float4 *>(lnp + C + c4) = lnv1;
+        if (NORM2) {
+            *reinterpret_cast<float4 *>(lnp + 2 * C + c4) = lnv2;
+            *reinterpret_cast<float4 *>(lnp + 3 * C + c4) = lnv3;
+        }
+    }
+    if (TABBED || a.owner) {
+        FFW_ISSUE(tile, tr, tw, own)
+    } else {  // no owner list: nothing to wait for (`own` as a merged value cost a vmcnt(0) behind W1 on this path too)
+        rx = *reinterpret_cast<const float4 *>(a.x_new + (size_t)min(tile * 16 + r, n - 1) * C + 4 * q);
+    }
+    int4 trn = tr;
+    float4 twn = tw;
+    int ownn = own;
+    FFW_TAB(min(tile + tstep, tend - 1), trn, twn, ownn)
+    // (the biases in front of W2: GEMM1(t0) starts from b1)
     float bias1[2][4];
 #pragma unroll
     for (int T = 0; T < 2; ++T)
 #pragma unroll
         for (int i = 0; i < 4; ++i) bias1[T][i] = a.b1[32 * wv + 16 * T + 4 * g + i];
     const float4 bias2 = *reinterpret_cast<const float4 *>(a.b2 + 16 * wv + 4 * g);  // MFMA view: channels 16 wv + 4 g + i
-    // row-wise constants of this lane's 4 channels
-    // (kept in LDS, not in 16 VGPRs: with the weights in 128 registers the loop sits at the 256-register limit, and every
-    // register less is a spill or a v_mov less; four ds_read_b128 per tile)
-    if (threadIdx.x < C / 4) {
-        const int c4 = threadIdx.x * 4;
-        *reinterpret_cast<float4 *>(lnp + c4) = *reinterpret_cast<const float4 *>(a.ln_w + c4);
-        *reinterpret_cast<float4 *>(lnp + C + c4) = *reinterpret_cast<const float4 *>(a.ln_b + c4);
-        if (NORM2) {
-            *reinterpret_cast<float4 *>(lnp + 2 * C + c4) = *reinterpret_cast<const float4 *>(a.ln2_w + c4);
-            *reinterpret_cast<float4 *>(lnp + 3 * C + c4) = *reinterpret_cast<const float4 *>(a.ln2_b + c4);
+    __builtin_amdgcn_sched_barrier(0);
+    if (packed) {
+        const h16x8 *wsrc = packed + woff;
+#pragma unroll
+        for (int ks = 0; ks < NW; ++ks) {
+            W2h[ks] = wsrc[(4 * NP + 2 * ks) * 64];
+            W2l[ks] = wsrc[(4 * NP + 2 * ks + 1) * 64];
+        }
+    } else {
+#pragma unroll
+        for (int ks = 0; ks < NW; ++ks) {
+            const float *src = a.W2 + (size_t)(16 * wv + la) * FF + 32 * ks + 4 * g;
+            ffw_raw8(src, src + 16, W2h[ks], W2l[ks]);
         }
     }
+    __builtin_amdgcn_sched_barrier(0);
+    WSTAMP(7)
+    if (!packed) {  // fp32 words -> fragments, every weight waited for here as before: not the product path
+#pragma unroll
+        for (int T = 0; T < 2; ++T)
+#pragma unroll
+            for (int P = 0; P < NP; ++P) ffw_split_raw8(W1h[T][P], W1l[T][P]);
+#pragma unroll
+        for (int ks = 0; ks < NW; ++ks) ffw_split_raw8(W2h[ks], W2l[ks]);
+    }
+    WSTAMP(8)
     __syncthreads();
+    WSTAMP(10)
 #define FFW_LNW *reinterpret_cast<const float4 *>(lnp + 4 * q)
 #define FFW_LNB *reinterpret_cast<const float4 *>(lnp + C + 4 * q)
 #define FFW_LN2W *reinterpret_cast<const float4 *>(lnp + 2 * C + 4 * q)
@@ -759,8 +849,8 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
     //   I2(t) = { GEMM2(t) -> y tile  |  A(t+1): x, LayerNorm, split -> B fragments; row gathers of t+2 leave }  [barrier]
     //   I1(t) = { D(t): y tile + x -> y, next LayerNorm, stores  |  GEMM1(t+1) -> this wave's k-slice of u }     [barrier]
     // bfrag(t+1) is written while the others may still be in GEMM2(t) (everybody is past GEMM1(t)); ufrag(t+1) and the
-    // reads of ytile(t) share an interval (everybody is past GEMM2(t)).  Past the last tile the pipeline repeats the
-    // last tile (A and GEMM1 once more, results unused) instead of branching.
+    // reads of ytile(t) share an interval (everybody is past GEMM2(t)).  The loop runs while a next tile exists; a workgroup's
+    // last tile (its only one: straight from the head) takes the peeled tail below, GEMM2 and D alone.
     float4 xc;
     FFW_COMBINE(xc)
     {
@@ -769,7 +859,9 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
         FFW_TAB(min(t1 + tstep, tend - 1), trn, twn, ownn)
     }
     FFW_NORM_TO_BFRAG(xc)
+    WSTAMP(11)
     __syncthreads();
+    WSTAMP(12)
     FFW_GEMM1()
     WSTAMP(0)
     __syncthreads();
@@ -781,10 +873,37 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
     // the later-dispatched half of the workgroup -- the loser of every issue arbitration on its SIMD, MI355X_MICROARCH.md "Two
     // waves per SIMD" item 4 -- runs at static priority 1: 46.4 -> 46.0 and 47.4 -> 46.5 us on two boxes
     if (wv >= NW / 2) __builtin_amdgcn_s_setprio(1);
-    for (;;) {
-        const int tile_next = tile + tstep;
-        const bool has_next = tile_next < tend;
-        const int t1 = has_next ? tile_next : tile;  // the tile whose A / GEMM1 run in this iteration
+    // the sums of GEMM2 -> this wave's 16 channels of the y tile
+#define FFW_YTILE(m_, l_, k_)                                                                               \
+    {                                                                                                       \
+        const f32x2 y01 = pk_fma(pk2(l_[0], l_[1]) + pk2(k_[0], k_[1]), pk1(SPLIT_INV), pk2(m_[0], m_[1])), \
+                    y23 = pk_fma(pk2(l_[2], l_[3]) + pk2(k_[2], k_[3]), pk1(SPLIT_INV), pk2(m_[2], m_[3])); \
+        *reinterpret_cast<float4 *>(ytile + la * PS + 16 * wv + 4 * g) = make_float4(y01[0], y01[1], y23[0], y23[1]); \
+    }
+    // the four pieces of D on  yt (this lane's piece of the y tile), xc, row -> y01, y23, d01, d23, var
+#define FFW_D_Y()                                                                                           \
+    y01 = pk2(yt.x, yt.y) + pk2(xc.x, xc.y);                                                                \
+    y23 = pk2(yt.z, yt.w) + pk2(xc.z, xc.w);                                                                \
+    if (STOREY) *reinterpret_cast<float4 *>(a.y + row * C + 4 * q) = make_float4(y01[0], y01[1], y23[0], y23[1]);
+#define FFW_D_MEAN()                                                                                        \
+    {                                                                                                       \
+        const float mean = ffw_row_sum<LPR>((y01[0] + y01[1]) + (y23[0] + y23[1])) * (1.0f / C);            \
+        d01 = y01 - pk1(mean);                                                                              \
+        d23 = y23 - pk1(mean);                                                                              \
+    }
+#define FFW_D_VAR()                                                                                         \
+    var = ffw_row_sum<LPR>(                                                                                 \
+        __builtin_fmaf(d23[1], d23[1], __builtin_fmaf(d23[0], d23[0], __builtin_fmaf(d01[1], d01[1], d01[0] * d01[0]))));
+#define FFW_D_NORM()                                                                                        \
+    {                                                                                                       \
+        const float rstd = rsqrtf(var * (1.0f / C) + a.eps2);                                               \
+        const float4 ln2w = FFW_LN2W, ln2b = FFW_LN2B;                                                      \
+        const f32x2 n01 = d01 * pk1(rstd) * pk2(ln2w.x, ln2w.y) + pk2(ln2b.x, ln2b.y),                      \
+                    n23 = d23 * pk1(rstd) * pk2(ln2w.z, ln2w.w) + pk2(ln2b.z, ln2b.w);                      \
+        *reinterpret_cast<float4 *>(a.y_norm + row * C + 4 * q) = make_float4(n01[0], n01[1], n23[0], n23[1]); \
+    }
+    while (tile + tstep < tend) {
+        const int t1 = tile + tstep;  // the tile whose A / GEMM1 run in this iteration
         WSTAMP(1)
         // ---- I2: GEMM2(t): this wave's 16 output channels over all k-slices | A(t1) ------------------------------
         float4 xn;
@@ -838,11 +957,7 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
                 ulo = ulon;
                 __builtin_amdgcn_sched_barrier(0);
             }
-            {
-                const f32x2 y01 = pk_fma(pk2(l[0], l[1]) + pk2(k[0], k[1]), pk1(SPLIT_INV), pk2(m[0], m[1])),
-                            y23 = pk_fma(pk2(l[2], l[3]) + pk2(k[2], k[3]), pk1(SPLIT_INV), pk2(m[2], m[3]));
-                *reinterpret_cast<float4 *>(ytile + la * PS + 16 * wv + 4 * g) = make_float4(y01[0], y01[1], y23[0], y23[1]);
-            }
+            FFW_YTILE(m, l, k)
         }
         WSTAMP(2)
         __syncthreads();
@@ -881,22 +996,13 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
 #pragma unroll
                 for (int pc = st * PPS1; pc < (st + 1) * PPS1 && pc < 4 && st < NP; ++pc) {
                     if (pc == 0) {
-                        y01 = pk2(yt.x, yt.y) + pk2(xc.x, xc.y);
-                        y23 = pk2(yt.z, yt.w) + pk2(xc.z, xc.w);
-                        if (STOREY) *reinterpret_cast<float4 *>(a.y + row * C + 4 * q) = make_float4(y01[0], y01[1], y23[0], y23[1]);
+                        FFW_D_Y()
                     } else if (pc == 1 && NORM2) {
-                        const float mean = ffw_row_sum<LPR>((y01[0] + y01[1]) + (y23[0] + y23[1])) * (1.0f / C);
-                        d01 = y01 - pk1(mean);
-                        d23 = y23 - pk1(mean);
+                        FFW_D_MEAN()
                     } else if (pc == 2 && NORM2) {
-                        var = ffw_row_sum<LPR>(
-                            __builtin_fmaf(d23[1], d23[1], __builtin_fmaf(d23[0], d23[0], __builtin_fmaf(d01[1], d01[1], d01[0] * d01[0]))));
+                        FFW_D_VAR()
                     } else if (pc == 3 && NORM2) {
-                        const float rstd = rsqrtf(var * (1.0f / C) + a.eps2);
-                        const float4 ln2w = FFW_LN2W, ln2b = FFW_LN2B;
-                        const f32x2 n01 = d01 * pk1(rstd) * pk2(ln2w.x, ln2w.y) + pk2(ln2b.x, ln2b.y),
-                                    n23 = d23 * pk1(rstd) * pk2(ln2w.z, ln2w.w) + pk2(ln2b.z, ln2b.w);
-                        *reinterpret_cast<float4 *>(a.y_norm + row * C + 4 * q) = make_float4(n01[0], n01[1], n23[0], n23[1]);
+                        FFW_D_NORM()
                     }
                 }
                 if (st == (NP + 1 < NS1 ? NP + 1 : NS1 - 1)) split4_rtz(FFW_U2(0, 0), FFW_U2(0, 2), h0_, l0_);
@@ -914,10 +1020,56 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
         ++ws_tiles;
 #endif
         xc = xn;
-        if (!has_next) break;
-        tile = tile_next;
+        tile = t1;
     }
+    WSTAMP(1)
+#ifdef MSSVT_STAMPS
+    ws_last = ws_t;
+#endif
+    // ---- tail, the workgroup's last tile: GEMM2(t) alone, barrier, D(t) alone.  No A or GEMM1 of a tile that does not exist,
+    // no gathers or table words (the look-ahead of the last steady iteration, clamped, is the last one issued)
+    {
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int lane = lane_t, la = lane & 15, g = lane >> 4;
+        f32x4 m = f32x4{bias2.x, bias2.y, bias2.z, bias2.w}, l = f32x4{0.f, 0.f, 0.f, 0.f}, k = l;
+#pragma unroll
+        for (int ks = 0; ks < NW; ++ks) {
+            const h16x8 uh = ufrag[(ks * 2) * 64 + lane], ulo = ufrag[(ks * 2 + 1) * 64 + lane];
+            MFMA_H(m, W2h[ks], uh);
+            MFMA_H(l, W2h[ks], ulo);
+            MFMA_H(k, W2l[ks], uh);
+        }
+        FFW_YTILE(m, l, k)
+    }
+    WSTAMP(14)
+    __syncthreads();
+    {
+        int lane_t = lane;
+        asm volatile("" : "+v"(lane_t));
+        const int lane = lane_t, r = wv * RPW + lane / LPR, q = lane % LPR;
+        const size_t row = (size_t)min(tile * 16 + r, n - 1);
+        const float4 yt = *reinterpret_cast<const float4 *>(ytile + r * PS + 4 * q);
+        f32x2 y01, y23, d01, d23;
+        float var;
+        FFW_D_Y()
+        if (NORM2) {
+            FFW_D_MEAN()
+            FFW_D_VAR()
+            FFW_D_NORM()
+        }
+    }
+    WSTAMP(15)
     WSTAMP(6)
+#ifdef MSSVT_STAMPS
+    ws_acc[13] = ws_t - ws_last;  // the workgroup's last tile, loop top to exit
+#endif
+#undef FFW_YTILE
+#undef FFW_D_Y
+#undef FFW_D_MEAN
+#undef FFW_D_VAR
+#undef FFW_D_NORM
+#undef FFW_DEAL
 #undef FFW_COMBINE
 #undef FFW_NORM_TO_BFRAG
 #undef FFW_GEMM1
@@ -926,7 +1078,7 @@ __global__ void __launch_bounds__((FF / 32) * MSSVT_WAVE, 1) k_ffn_ws(FfnArgs a,
 #ifdef MSSVT_STAMPS
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_ws_span[2 * blockIdx.x + 1] = __builtin_amdgcn_s_memrealtime();
     if (lane == 0 && blockIdx.x < 4) {
-        for (int k = 0; k < 7; ++k) g_ws_stamps[(blockIdx.x * 8 + (wv & 7)) * 16 + k] = ws_acc[k];
+        for (int k = 0; k < 16; ++k) g_ws_stamps[(blockIdx.x * 8 + (wv & 7)) * 16 + k] = ws_acc[k];
         g_ws_stamps[(blockIdx.x * 8 + (wv & 7)) * 16 + 9] = ws_tiles;
     }
 #endif
@@ -949,17 +1101,23 @@ static int launch_ffn_ws(const FfnArgs &a, const void *packed, hipStream_t strea
     if (grid < 1) return MSSVT_OK;
     const h16x8 *pk = reinterpret_cast<const h16x8 *>(packed);
     const dim3 block(NW * MSSVT_WAVE);
+#define FFW_LAUNCH(TABBED_, NORM2_, STOREY_)                                                                \
+    {                                                                                                       \
+        if (a.n_rows_dev) k_ffn_ws<C, FF, TABBED_, NORM2_, STOREY_, true><<<grid, block, lds, stream>>>(a, pk); \
+        else k_ffn_ws<C, FF, TABBED_, NORM2_, STOREY_, false><<<grid, block, lds, stream>>>(a, pk);         \
+    }
     if (a.tab_row && a.y_norm && !a.y) {
-        k_ffn_ws<C, FF, true, true, false><<<grid, block, lds, stream>>>(a, pk);
+        FFW_LAUNCH(true, true, false)
     } else if (!a.y) {
         return MSSVT_E_BADARG;
     } else if (a.tab_row) {
-        if (a.y_norm) k_ffn_ws<C, FF, true, true><<<grid, block, lds, stream>>>(a, pk);
-        else k_ffn_ws<C, FF, true, false><<<grid, block, lds, stream>>>(a, pk);
+        if (a.y_norm) FFW_LAUNCH(true, true, true)
+        else FFW_LAUNCH(true, false, true)
     } else {
-        if (a.y_norm) k_ffn_ws<C, FF, false, true><<<grid, block, lds, stream>>>(a, pk);
-        else k_ffn_ws<C, FF, false, false><<<grid, block, lds, stream>>>(a, pk);
+        if (a.y_norm) FFW_LAUNCH(false, true, true)
+        else FFW_LAUNCH(false, false, true)
     }
+#undef FFW_LAUNCH
     return mssvt_launch_status();
 }
 
